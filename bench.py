@@ -8,6 +8,8 @@ update).  Synthetic data: 10M rows x 28 float32 features with a non-linear label
 held-out synthetic set is reported for parity checks.
 
   python bench.py --gpus 1 --steps 50 --warmup 5
+  python bench.py --gpus 1 --steps 50 --warmup 5 --full                # + held-out AUC parity
+  python bench.py --gpus 1 --steps 50 --warmup 5 --dump-outputs DIR    # + the last step's outputs
   python -m torch.distributed.run --nnodes=1 --nproc-per-node 8 --master-addr 127.0.0.1 \
       --master-port 29500 bench.py --gpus 8 --steps 50 --warmup 5
 
@@ -17,9 +19,21 @@ the feature owners and all-gathers the owners' results over the peer communicato
 per collective reading the peers' HBM over xGMI; RCCL with LGBM_AMD_DEVICE_COMM=rccl).  Strong
 scaling: the total work is fixed, and the trees equal the 1-GPU trees.
 
-AUC parity: `auc_ref` is the held-out AUC of the same run (rows, generator seeds, tree count)
+A plain run sets up, warms up, times the steps and prints the result line.  Everything else
+is behind --full:
+
+AUC parity (--full): `auc_heldout` is the model's AUC on held-out rows of the same generator,
+`auc_ref` the held-out AUC of the same run (rows, generator seeds, tree count)
 trained by this framework's CPU learner, which grows the reference CLI's trees byte for byte
 (tests/test_golden.py); the values are pinned in tools/bench_auc_ref.json.
+
+--dump-outputs DIR writes what the last timed step left with its caller, as float64 .npy
+files (rank 0's, about 17 MB at 10M rows): `train_pred.npy`, the booster's predictions for a
+fixed, seeded sample of 2^20 of its training rows after that step, `train_pred_rows.npy`, the
+sample's row indices (float64 like every file of the dump; exact below 2^53), and
+`last_tree_<field>.npy`, the tree that step added (the fields of the model text: split features,
+thresholds, children, leaf values, weights and counts).  The data, the parameters and the sample depend on the
+arguments alone, so two builds run with the same arguments are compared file by file.
 """
 import argparse
 import json
@@ -71,6 +85,31 @@ def growth_stats(booster):
     return list(out)
 
 
+DUMP_SAMPLE_ROWS = 1 << 20
+DUMP_SAMPLE_SEED = 20240601
+TREE_FIELDS = ("split_feature", "split_gain", "threshold", "decision_type", "left_child", "right_child",
+               "leaf_value", "leaf_weight", "leaf_count", "internal_value", "internal_weight", "internal_count")
+
+
+def dump_outputs(booster, directory):
+    """The last step's outputs as DIR/<name>.npy (float64): the training rows' predictions after
+    it (a fixed seeded sample of DUMP_SAMPLE_ROWS rows when there are more) and the tree it added."""
+    os.makedirs(directory, exist_ok=True)
+    pred = booster._dataset_scores(0)
+    rows = np.arange(len(pred), dtype=np.int64)
+    if len(pred) > DUMP_SAMPLE_ROWS:
+        rows = np.sort(np.random.default_rng(DUMP_SAMPLE_SEED).choice(len(pred), DUMP_SAMPLE_ROWS, replace=False))
+    out = {"train_pred_rows": rows.astype(np.float64), "train_pred": np.asarray(pred[rows], dtype=np.float64)}
+    text = booster.model_to_string(start_iteration=booster.current_iteration() - 1, num_iteration=1)
+    tree = text[text.index("Tree=0"):text.index("end of trees")]
+    fields = dict(line.split("=", 1) for line in tree.splitlines() if "=" in line)
+    for k in TREE_FIELDS:
+        if k in fields:
+            out["last_tree_" + k] = np.array(fields[k].split(), dtype=np.float64)
+    for name, a in out.items():
+        np.save(os.path.join(directory, name + ".npy"), a)
+
+
 def _device_sync(lgb):
     """Drain the device queue around the timed region (the learner's own HIP runtime;
     torch.cuda.synchronize() as well when torch already drives a GPU in this process)."""
@@ -98,6 +137,12 @@ def main():
     ap.add_argument("--eval-train", action="store_true",
                     help="evaluate the training AUC after every iteration inside the timed loop "
                          "(valid_sets=[dtrain] cost; device-resident metric)")
+    ap.add_argument("--full", action="store_true",
+                    help="also score the model on --test-rows held-out rows and compare with the pinned "
+                         "CPU-learner AUC (auc_heldout, auc_ref, auc_delta); a plain run only times the steps")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the last step's outputs (training predictions of a "
+                         "fixed row sample, the tree it added) as DIR/<name>.npy")
     args = ap.parse_args()
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -160,14 +205,19 @@ def main():
         diag = {"rounds_per_tree": round(d[2] / max(1.0, d[0]), 2),
                 "collective_bytes_per_iter": round(d[5] / args.steps),
                 "speculated_trees": int(d[6])}
-    auc = None
-    if rank == 0 and args.test_rows > 0:
-        Xt, yt = make_rows(n_total + 12345678, args.test_rows, args.features)
-        auc = roc_auc(yt, booster.predict(Xt))
-    ref = auc_reference(n_total, args.features, args.leaves, args.max_bin, args.test_rows, booster.num_trees(),
-                        json.loads(args.params)) if args.device == "gpu" else None
-    auc_fields = {"auc_ref": ref["auc"] if ref else None,
-                  "auc_delta": float("%.3g" % (auc - ref["auc"])) if ref and auc is not None else None}
+    if rank == 0 and args.dump_outputs and args.steps > 0:
+        dump_outputs(booster, args.dump_outputs)
+    auc_fields = {}
+    if args.full:
+        auc = None
+        if rank == 0 and args.test_rows > 0:
+            Xt, yt = make_rows(n_total + 12345678, args.test_rows, args.features)
+            auc = roc_auc(yt, booster.predict(Xt))
+        ref = auc_reference(n_total, args.features, args.leaves, args.max_bin, args.test_rows, booster.num_trees(),
+                            json.loads(args.params)) if args.device == "gpu" else None
+        auc_fields = {"auc_heldout": auc,
+                      "auc_ref": ref["auc"] if ref else None,
+                      "auc_delta": float("%.3g" % (auc - ref["auc"])) if ref and auc is not None else None}
     if rank == 0:
         print(json.dumps({
             "metric": "sec/iteration (500 trees, 255 bins, 63 leaves) on Higgs-shaped 10Mx28; AUC parity",
@@ -188,7 +238,6 @@ def main():
             "config": {"model": "gbdt binary, num_leaves={}, max_bin={}".format(args.leaves, args.max_bin),
                        "global_batch": n_total, "seq_len": args.features,
                        "parallelism": "dp{}".format(world) if world > 1 else "single"},
-            "auc_heldout": auc,
             **auc_fields,
             "trees": booster.num_trees(),
             "device_comm": torch_dist.device_comm_kind() if world > 1 else None,

@@ -22,6 +22,7 @@
 #include <cstring>
 #include <memory>
 #include <string>
+#include <thread>
 #include <vector>
 
 #include "../device/kernels.h"
@@ -154,7 +155,13 @@ class PeerComm : public DeviceComm {
   bool AsyncError(std::string* msg) override {
     const unsigned code = __atomic_load_n(&status_[0], __ATOMIC_ACQUIRE);
     if (code == dev::kPeerOk) return false;
-    const unsigned ep = __atomic_load_n(&status_[2], __ATOMIC_ACQUIRE);
+    // the kernel writes the code, then the epoch (two stores to host memory; epochs start at 1):
+    // a reader that saw the code gives the epoch a moment to land
+    unsigned ep = __atomic_load_n(&status_[2], __ATOMIC_ACQUIRE);
+    for (int i = 0; ep == 0 && i < 2000; ++i) {
+      std::this_thread::sleep_for(std::chrono::microseconds(50));
+      ep = __atomic_load_n(&status_[2], __ATOMIC_ACQUIRE);
+    }
     static const char* what[] = {"ok", "timed out waiting for a peer rank", "injected fault", "aborted"};
     *msg = std::string("peer device collective ") + (code < 4 ? what[code] : "failed") + " (rank " +
            std::to_string(rank_) + ", collective " + std::to_string(ep) + ")";

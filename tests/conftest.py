@@ -41,6 +41,31 @@ def _native_library():
 
 
 @pytest.fixture(scope="session")
+def example_data(tmp_path_factory):
+    """The reference's bundled example datasets, one directory per example, put together once per
+    session: binary_classification and regression from tests/data/examples, multiclass_classification,
+    lambdarank and xendcg from tests/golden/examples (data and side files gzipped, train.conf without
+    its comments).  xendcg trains on lambdarank's data files, stored once."""
+    import gzip
+    import shutil
+    dst = str(tmp_path_factory.mktemp("examples"))
+    for src in (os.path.join(ROOT, "tests", "data", "examples"), os.path.join(ROOT, "tests", "golden", "examples")):
+        for name in sorted(os.listdir(src)):
+            os.makedirs(os.path.join(dst, name))
+            for f in os.listdir(os.path.join(src, name)):
+                if f.endswith(".gz"):
+                    with gzip.open(os.path.join(src, name, f), "rb") as i, \
+                            open(os.path.join(dst, name, f[:-3]), "wb") as o:
+                        shutil.copyfileobj(i, o)
+                else:
+                    shutil.copyfile(os.path.join(src, name, f), os.path.join(dst, name, f))
+    for f in os.listdir(os.path.join(dst, "lambdarank")):
+        if f != "train.conf":
+            shutil.copyfile(os.path.join(dst, "lambdarank", f), os.path.join(dst, "xendcg", f))
+    return dst
+
+
+@pytest.fixture(scope="session")
 def gpu_available():
     import lightgbmv1_amd as lgb
     n = lgb.device_count()

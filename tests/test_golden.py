@@ -1,8 +1,10 @@
 """Parity against the reference itself: the golden oracle of SURVEY.md §7.7-10 / §7.8.
 
 The oracle is the reference's CPU command line program compiled from its own sources in a
-scratch copy (``tools/build_golden.sh``: USE_GPU=OFF, nothing prebuilt is run); ``LGBM_GOLDEN_CLI``
-points at it (default /tmp/refbuild/lightgbm).  The tests skip when it is absent.
+scratch copy (``oracle/build_ref.sh``: USE_GPU=OFF, nothing prebuilt is run; ``build()`` of
+``__graft_entry__.py`` runs it where a checkout of the reference is at hand); ``LGBM_GOLDEN_CLI``
+points at it (default oracle/_ref/lightgbm).  The tests skip when it is absent.  The example
+data are the copies in the repository (conftest.py's ``example_data``).
 
 * ``test_reference_models_predict_identically``: models the reference trains on its bundled
   examples (binary with weights, regression with init scores, multiclass, lambdarank) load here
@@ -26,13 +28,12 @@ import pytest
 
 import lightgbmv1_amd as lgb
 
-ORACLE = os.environ.get("LGBM_GOLDEN_CLI", "/tmp/refbuild/lightgbm")
-OUR_CLI = os.path.join(os.path.dirname(lgb.__file__), "lib", "lightgbm")
 HERE = os.path.dirname(os.path.abspath(__file__))
-REF_EXAMPLES = os.environ.get("LGBM_AMD_REF_EXAMPLES", "/root/reference/examples")
+ORACLE = os.environ.get("LGBM_GOLDEN_CLI", os.path.join(os.path.dirname(HERE), "oracle", "_ref", "lightgbm"))
+OUR_CLI = os.path.join(os.path.dirname(lgb.__file__), "lib", "lightgbm")
 
 pytestmark = pytest.mark.skipif(not os.access(ORACLE, os.X_OK),
-                                reason="golden oracle not built (tools/build_golden.sh): " + ORACLE)
+                                reason="golden oracle not built (oracle/build_ref.sh): " + ORACLE)
 
 # (example directory, file prefix, test data file)
 EXAMPLES = [("binary_classification", "binary", "binary.test"),
@@ -41,16 +42,10 @@ EXAMPLES = [("binary_classification", "binary", "binary.test"),
             ("lambdarank", "rank", "rank.test")]
 
 
-def _example(tmp_path, name):
-    for root in (REF_EXAMPLES, os.path.join(HERE, "data", "examples")):
-        src = os.path.join(root, name)
-        if os.path.isdir(src):
-            dst = tmp_path / name
-            shutil.copytree(src, dst)
-            for f in dst.iterdir():
-                os.chmod(f, 0o644)
-            return dst
-    pytest.skip("example %s not available" % name)
+def _example(tmp_path, root, name):
+    dst = tmp_path / name
+    shutil.copytree(os.path.join(root, name), dst)
+    return dst
 
 
 def _run(cli, cwd, *args):
@@ -81,8 +76,8 @@ def _trees(model_text):
 
 
 @pytest.mark.parametrize("name,prefix,test_file", EXAMPLES, ids=[e[0] for e in EXAMPLES])
-def test_reference_models_predict_identically(tmp_path, name, prefix, test_file):
-    d = _example(tmp_path, name)
+def test_reference_models_predict_identically(tmp_path, example_data, name, prefix, test_file):
+    d = _example(tmp_path, example_data, name)
     _run(ORACLE, d, *(_train_args(20) + ["output_model=ref_model.txt"]))
     _run(ORACLE, d, "task=predict", "data=" + test_file, "input_model=ref_model.txt", "output_result=ref_pred.txt",
          "verbosity=-1")
@@ -103,8 +98,8 @@ def test_reference_models_predict_identically(tmp_path, name, prefix, test_file)
 
 
 @pytest.mark.parametrize("name,prefix,test_file", EXAMPLES, ids=[e[0] for e in EXAMPLES])
-def test_cpu_learner_trees_match_reference(tmp_path, name, prefix, test_file):
-    d = _example(tmp_path, name)
+def test_cpu_learner_trees_match_reference(tmp_path, example_data, name, prefix, test_file):
+    d = _example(tmp_path, example_data, name)
     _run(ORACLE, d, *(_train_args(10) + ["output_model=ref_model.txt"]))
     _run(OUR_CLI, d, *(_train_args(10) + ["output_model=our_model.txt", "device_type=cpu"]))
     ref = _trees((d / "ref_model.txt").read_text())
@@ -162,7 +157,7 @@ BINARY_CASES = [("binary_classification", "binary.train", "binary.test"),
 
 
 @pytest.mark.parametrize("name,train_file,test_file", BINARY_CASES, ids=[c[0] for c in BINARY_CASES])
-def test_dataset_binary_files_interchange(tmp_path, monkeypatch, name, train_file, test_file):
+def test_dataset_binary_files_interchange(tmp_path, monkeypatch, example_data, name, train_file, test_file):
     """Dataset binary files (reference dataset.cpp:890-992 / dataset_loader.cpp:273-525): the
     reference's save_binary output and this framework's are the same bytes; each side trains
     from the other's file the trees it trains from the text file.  With host-sparse storage
@@ -176,7 +171,7 @@ def test_dataset_binary_files_interchange(tmp_path, monkeypatch, name, train_fil
         conf = ["task=train", "objective=binary", "data=" + train_file, "num_trees=8", "num_leaves=15",
                 "num_threads=4", "verbosity=-1"]
     else:
-        d = _example(tmp_path, name)
+        d = _example(tmp_path, example_data, name)
         conf = _train_args(8)
     ref_dir, our_dir = tmp_path / "ref_bin", tmp_path / "our_bin"
     shutil.copytree(d, ref_dir)

@@ -508,7 +508,8 @@ def test_bench_py_under_torchrun_two_processes(gpu_available, tmp_path):
     env = dict(os.environ, OMP_NUM_THREADS="4")
     out = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2",
                           "--master-addr", "127.0.0.1", "--master-port", str(port), os.path.join(root, "bench.py"),
-                          "--gpus", "2", "--steps", "5", "--warmup", "2", "--rows", "1000000", "--test-rows", "50000"],
+                          "--gpus", "2", "--steps", "5", "--warmup", "2", "--rows", "1000000", "--test-rows", "50000",
+                          "--full"],
                          cwd=str(tmp_path), env=env, capture_output=True, text=True, timeout=180)
     assert out.returncode == 0, out.stdout[-2000:] + out.stderr[-3000:]
     lines = [l for l in out.stdout.splitlines() if l.startswith("{")]

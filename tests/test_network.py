@@ -152,9 +152,7 @@ def test_mpi_transport_missing_library_raises(tmp_path):
     assert "error:" in out.stdout and "no MPI library" in out.stdout, out.stdout
 
 
-@pytest.mark.skipif(not os.path.isfile("/root/reference/examples/binary_classification/binary.train"),
-                    reason="reference examples not mounted")
-def test_mpi_transport_cli_finalizes(tmp_path):
+def test_mpi_transport_cli_finalizes(tmp_path, example_data):
     """The CLI over the MPI transport (two processes, data-parallel, rows split by rank) trains,
     writes the same model on both ranks and finalizes MPI at exit like the reference's main()
     (the stand-in library records MPI_Finalize)."""
@@ -162,7 +160,7 @@ def test_mpi_transport_cli_finalizes(tmp_path):
     mpi_dir = tmp_path / "mpi"
     mpi_dir.mkdir()
     cli = os.path.join(os.path.dirname(lgb.__file__), "lib", "lightgbm")
-    data = "/root/reference/examples/binary_classification/binary.train"
+    data = os.path.join(example_data, "binary_classification", "binary.train")
     procs = []
     for r in range(2):
         env = dict(os.environ, OMP_NUM_THREADS="2", LGBM_AMD_NETWORK="mpi", LGBM_AMD_MPI_LIB=lib,

@@ -9,9 +9,8 @@
   ``examples/*`` (binary with ``.weight``, multiclass, regression with ``.init``, lambdarank and
   xendcg with ``.query``): predictions from a matrix, from the text file and from the sklearn
   estimator agree, and a Dataset built from the file (side files loaded by name) matches the one
-  built from arrays.  The example data is read from the reference checkout (``LGBM_AMD_REF_EXAMPLES``
-  or /root/reference/examples), else from the binary / regression copies in tests/data/examples
-  (so the device variants run on the GPU box); the tests skip where it is absent.
+  built from arrays.  The example data are the copies in the repository (the
+  ``example_data`` fixture of conftest.py unpacks them).
 """
 import os
 
@@ -22,20 +21,6 @@ import lightgbmv1_amd as lgb
 
 LOWER = -2.9040190126976606
 UPPER = 3.3182142872462883
-_VENDORED = os.path.join(os.path.dirname(os.path.abspath(__file__)), "data", "examples")
-
-
-def _examples_root():
-    """LGBM_AMD_REF_EXAMPLES, else the reference checkout, else the copies of the binary and
-    regression examples vendored under tests/data/examples (the GPU box has no checkout)"""
-    env = os.environ.get("LGBM_AMD_REF_EXAMPLES")
-    if env:
-        return env
-    return "/root/reference/examples" if os.path.isdir("/root/reference/examples") else _VENDORED
-
-
-EXAMPLES = _examples_root()
-
 
 def _breast_cancer():
     sk_datasets = pytest.importorskip("sklearn.datasets")
@@ -92,10 +77,8 @@ def test_pinned_bounds_device(tmp_path, gpu_available):
 class _Example:
     """The reference's FileLoader: an example directory's train.conf as parameters."""
 
-    def __init__(self, directory, prefix):
-        self.directory = os.path.join(EXAMPLES, directory)
-        if not os.path.isdir(self.directory):
-            pytest.skip("reference examples not available: %s" % self.directory)
+    def __init__(self, root, directory, prefix):
+        self.directory = os.path.join(root, directory)
         self.prefix = prefix
         self.params = {"gpu_use_dp": True, "verbose": -1}
         with open(os.path.join(self.directory, "train.conf")) as f:
@@ -154,8 +137,8 @@ def _sk_params(fd):
     return {k: v for k, v in fd.params.items() if k not in ("data", "valid_data", "task")}
 
 
-def test_example_binary():
-    fd = _Example("binary_classification", "binary")
+def test_example_binary(example_data):
+    fd = _Example(example_data, "binary_classification", "binary")
     X_train, y_train, _ = fd.load_dataset(".train")
     X_test, _, X_test_fn = fd.load_dataset(".test")
     weight_train = fd.load_field(".train.weight")
@@ -167,8 +150,8 @@ def test_example_binary():
     fd.file_load_check(lgb_train, ".train")
 
 
-def test_example_multiclass():
-    fd = _Example("multiclass_classification", "multiclass")
+def test_example_multiclass(example_data):
+    fd = _Example(example_data, "multiclass_classification", "multiclass")
     X_train, y_train, _ = fd.load_dataset(".train")
     X_test, _, X_test_fn = fd.load_dataset(".test")
     lgb_train = lgb.Dataset(X_train, y_train)
@@ -179,8 +162,8 @@ def test_example_multiclass():
     fd.file_load_check(lgb_train, ".train")
 
 
-def test_example_regression():
-    fd = _Example("regression", "regression")
+def test_example_regression(example_data):
+    fd = _Example(example_data, "regression", "regression")
     X_train, y_train, _ = fd.load_dataset(".train")
     X_test, _, X_test_fn = fd.load_dataset(".test")
     init_score_train = fd.load_field(".train.init")
@@ -193,8 +176,8 @@ def test_example_regression():
 
 
 @pytest.mark.parametrize("example", ["lambdarank", "xendcg"])
-def test_example_ranking(example):
-    fd = _Example(example, "rank")
+def test_example_ranking(example, example_data):
+    fd = _Example(example_data, example, "rank")
     X_train, y_train, _ = fd.load_dataset(".train", is_sparse=True)
     X_test, _, X_test_fn = fd.load_dataset(".test", is_sparse=True)
     group_train = fd.load_field(".train.query")
@@ -211,15 +194,15 @@ def test_example_ranking(example):
 
 @pytest.mark.gpu
 @pytest.mark.parametrize("example", ["binary", "regression"])
-def test_example_device(example, gpu_available):
+def test_example_device(example, gpu_available, example_data):
     """The same consistency checks with the device learner (wide histograms, as the reference's
     GPU runs of these examples)."""
     if example == "binary":
-        fd = _Example("binary_classification", "binary")
+        fd = _Example(example_data, "binary_classification", "binary")
         side = {"weight": fd.load_field(".train.weight")}
         est = lgb.LGBMClassifier
     else:
-        fd = _Example("regression", "regression")
+        fd = _Example(example_data, "regression", "regression")
         side = {"init_score": fd.load_field(".train.init")}
         est = lgb.LGBMRegressor
     fd.params["device_type"] = "gpu"

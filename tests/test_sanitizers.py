@@ -1,7 +1,10 @@
 """Host-code sanitizer run: the CLI built with AddressSanitizer +
 UndefinedBehaviorSanitizer (`make sanitize`, built by the first test that needs it, ~1 min on
-8 cores) trains the reference's example configs on the CPU learner; any ASan / UBSan report
-fails the test."""
+8 cores) trains the reference's example configs (conftest.py's ``example_data``) on the CPU
+learner; any ASan / UBSan report fails the test.  The instrumented programs are host-code checks
+for machines without a GPU: where a HIP device is visible the tests skip before building anything
+(device code is never instrumented, and the sanitizer runtimes are kept away from the GPU driver
+stack)."""
 import fcntl
 import os
 import shutil
@@ -9,9 +12,10 @@ import subprocess
 
 import pytest
 
+import lightgbmv1_amd as lgb
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 ASAN_CLI = os.path.join(ROOT, "build_asan", "lightgbm")
-EXAMPLES = "/root/reference/examples"
 
 
 def _build(target, path):
@@ -30,18 +34,24 @@ def _build(target, path):
 
 
 @pytest.fixture(scope="module")
-def asan_cli():
+def host_only():
+    n = lgb.device_count()
+    if n > 0:
+        pytest.skip("host-code sanitizer programs run on machines without a GPU, found %d HIP device(s)" % n)
+
+
+@pytest.fixture(scope="module")
+def asan_cli(host_only):
     _build("sanitize", ASAN_CLI)
     return ASAN_CLI
 
 
-@pytest.mark.skipif(not os.path.isdir(EXAMPLES), reason="reference examples not mounted")
 @pytest.mark.parametrize("example,extra", [("binary_classification", ["num_trees=10"]),
                                            ("regression", ["num_trees=10"]),
                                            ("lambdarank", ["num_trees=5"])])
-def test_examples_clean_under_asan_ubsan(tmp_path, asan_cli, example, extra):
+def test_examples_clean_under_asan_ubsan(tmp_path, asan_cli, example_data, example, extra):
     work = tmp_path / example
-    shutil.copytree(os.path.join(EXAMPLES, example), work)
+    shutil.copytree(os.path.join(example_data, example), work)
     env = dict(os.environ, ASAN_OPTIONS="detect_leaks=1:abort_on_error=0", UBSAN_OPTIONS="print_stacktrace=1")
     out = subprocess.run([asan_cli, "config=train.conf", "output_model=" + str(tmp_path / "m.txt")] + extra,
                          cwd=work, env=env, capture_output=True, text=True, timeout=600)
@@ -54,15 +64,14 @@ def test_examples_clean_under_asan_ubsan(tmp_path, asan_cli, example, extra):
 TSAN_DRIVER = os.path.join(ROOT, "build_tsan", "tsan_driver")
 
 
-@pytest.mark.skipif(not os.path.isdir(EXAMPLES), reason="reference examples not mounted")
-def test_threads_clean_under_tsan(tmp_path):
+def test_threads_clean_under_tsan(tmp_path, host_only, example_data):
     """ThreadSanitizer (`make tsan`): two_round loading's reader thread, and training under the
     booster's exclusive lock while three threads predict and one reads evaluations through the
     C API (tests/native/tsan_driver.cpp).  Found and fixed with it: the log level written by
     every C API call, and booster getters reading the model without the lock."""
     _build("tsan", TSAN_DRIVER)
     env = dict(os.environ, OMP_NUM_THREADS="1", TSAN_OPTIONS="exitcode=66 halt_on_error=0")
-    out = subprocess.run([TSAN_DRIVER, os.path.join(EXAMPLES, "binary_classification", "binary.train"), "28"],
+    out = subprocess.run([TSAN_DRIVER, os.path.join(example_data, "binary_classification", "binary.train"), "28"],
                          cwd=tmp_path, env=env, capture_output=True, text=True, timeout=600)
     log = out.stdout + out.stderr
     assert "ThreadSanitizer" not in log, log[-6000:]
