@@ -74,6 +74,9 @@ class ScoreUpdater {
   bool host_stale_ = false;
 };
 
+// what a device prediction computes (GBDT::PredictDenseOnDevice)
+enum class DevicePredictKind { Normal, Raw, Leaf, Contrib };
+
 class GBDT {
  public:
   GBDT();
@@ -107,10 +110,23 @@ class GBDT {
   void InitPredict(int start_iteration, int num_iteration, bool is_pred_contrib);
   // InitPredict(start_iteration, num_iteration, false) would change nothing
   bool PredictRangeIs(int start_iteration, int num_iteration) const;
-  // normal / raw predictions of a dense float32 / float64 matrix on the MI355X (same results
-  // as the host predictor); false if not applicable (no device, too many classes)
+  // predictions of a dense float32 / float64 matrix on the MI355X: normal / raw scores and leaf
+  // indices as the host predictor gives them, contributions from per-leaf path tables (equal to
+  // the host's recursion up to rounding).  Rows pass through the device in chunks that fit its
+  // free memory.  false if not applicable: no device, too many classes, or for contributions a
+  // path longer than the kernel holds or a node without data_count (the host then predicts)
   bool PredictDenseOnDevice(const void* data, bool is_double, int64_t nrow, int ncol, bool row_major,
-                            int start_iteration, int num_iteration, bool raw, double* out);
+                            int start_iteration, int num_iteration, DevicePredictKind kind, double* out);
+  // the same kernels on a row-major matrix in device memory, into out_len doubles of device
+  // memory (raw scores, leaf indices or contributions); what is not applicable is an error
+  void PredictDeviceBuffers(const void* d_data, bool is_double, int64_t nrow, int ncol, int start_iteration,
+                            int num_iteration, DevicePredictKind kind, double* d_out, int64_t out_len);
+  // predictions this process has computed on the device (tests: which path a call took)
+  static int64_t DevicePredictions();
+  // contributions of row-major float64 host rows from the path tables the device kernel reads,
+  // evaluated on the host with the kernel's arithmetic (tests; needs no device)
+  void ContribFromPathTables(const double* data, int64_t nrow, int ncol, int start_iteration, int num_iteration,
+                             double* out);
   int NumPredictOneRow(int start_iteration, int num_iteration, bool is_pred_leaf, bool is_pred_contrib) const;
   void PredictRaw(const double* features, double* output, const PredictionEarlyStopInstance* es) const;
   void Predict(const double* features, double* output, const PredictionEarlyStopInstance* es) const;
@@ -218,6 +234,8 @@ class GBDT {
   double shrinkage_rate_ = 0.1;
   int num_iteration_for_pred_ = 0;
   int start_iteration_for_pred_ = 0;
+  // InitPredict, then the trees of the prediction window in model order
+  std::vector<const Tree*> PredictWindowTrees(int start_iteration, int num_iteration);
   int num_init_iteration_ = 0;
   std::vector<std::string> feature_names_;
   std::vector<std::string> feature_infos_;

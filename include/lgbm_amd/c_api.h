@@ -250,6 +250,15 @@ LIGHTGBM_C_EXPORT int LGBM_AMD_BoosterDeviceGradients(BoosterHandle handle, floa
 // JSON report of the leaves' device best splits checked against the CPU split finder
 LIGHTGBM_C_EXPORT int LGBM_AMD_BoosterDeviceCheckSplits(BoosterHandle handle, int64_t buffer_len, int64_t* out_len,
                                                         char* out_str);
+// SHAP contributions of row-major float64 rows from the per-leaf path tables the device kernel
+// reads, evaluated on the host with the kernel's arithmetic (no GPU needed): separates wrong
+// tables from a wrong kernel; same output layout as C_API_PREDICT_CONTRIB
+LIGHTGBM_C_EXPORT int LGBM_AMD_BoosterPathTableContrib(BoosterHandle handle, const double* data, int32_t nrow,
+                                                       int32_t ncol, int start_iteration, int num_iteration,
+                                                       int64_t* out_len, double* out_result);
+// predictions this process has computed on the device, over all boosters (tests: whether a call
+// took the device path or the host predictor)
+LIGHTGBM_C_EXPORT int LGBM_AMD_DevicePredictCount(int64_t* out);
 // for external collective functions (LGBM_NetworkInitWithFunctions) that fail: makes the
 // collective that called them raise on this thread instead of using an unfilled buffer
 LIGHTGBM_C_EXPORT int LGBM_AMD_NetworkReportExternalError(const char* msg);

@@ -87,6 +87,8 @@ class Tree {
   std::string ToIfElse(int index, bool predict_leaf_index) const;
 
   void RecomputeMaxDepth();
+  // the data-weighted mean leaf value: the contribution column past the features
+  double ExpectedValue() const;
   int max_depth() const { return max_depth_; }
 
   static bool IsZero(double v) { return v >= -kZeroThreshold && v <= kZeroThreshold; }
@@ -112,7 +114,6 @@ class Tree {
   std::string NodeToIfElseByMap(int index, bool predict_leaf_index) const;
   std::string NumericalDecisionIfElse(int node) const;
   std::string CategoricalDecisionIfElse(int node) const;
-  double ExpectedValue() const;
 
   struct PathElement {
     int feature_index;

@@ -76,6 +76,7 @@ constexpr int kQueryMetricDeviceMaxDocs = 16384;
   X(HistTileWords, "LGBM_AMD_HIST_TILE_WORDS", "n: histogram column tile width (words)")                       \
   X(HistRowsCap, "LGBM_AMD_HIST_ROWS_CAP", "n: rows per partial histogram block")                              \
   X(TextBlockBytes, "LGBM_AMD_TEXT_BLOCK_BYTES", "n: text reader block size (tests)")                          \
+  X(PredictChunkRows, "LGBM_AMD_PREDICT_CHUNK_ROWS", "n: rows per chunk of a device prediction (tests; auto from free memory)")  \
   /* tuning (same models; defaults above) */                                                                   \
   X(RoundK, "LGBM_AMD_ROUND_K", "n: expansions per round, fixed (1: one split per step)")                      \
   X(RoundVmax, "LGBM_AMD_ROUND_VMAX", "n: speculation depth below a leaf (14)")                                \

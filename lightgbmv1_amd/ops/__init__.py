@@ -11,6 +11,9 @@ the kernels can be checked one by one against plain PyTorch references
   reference src/metric/*.hpp Eval)
 * :func:`sample_rows` -- bagging / GOSS row sampling with the reference's per-1024-row
   generators (src/device/sample_kernels.hip; reference gbdt.cpp:162-243, goss.hpp:103-179)
+* :func:`forest_predict` -- a trained booster's raw scores, leaf indices or SHAP
+  contributions of a matrix that already is on the GPU (src/device/predict_kernels.hip,
+  src/device/shap_kernels.hip; reference gbdt_prediction.cpp, Tree::TreeSHAP)
 
 There is no host fallback: the ops need a GPU and the in-tree library.
 """
@@ -18,10 +21,10 @@ import ctypes
 
 import numpy as np
 
-from .._native import LightGBMError, params_str as param_dict_to_str
+from .._native import LightGBMError, call as _native_call, params_str as param_dict_to_str
 from ..basic import _load_lib
 
-__all__ = ["gradients", "metric", "sample_rows"]
+__all__ = ["gradients", "metric", "sample_rows", "forest_predict"]
 
 
 def _torch():
@@ -126,3 +129,33 @@ def sample_rows(n, fraction=1.0, seed=3, goss=False, top_rate=0.2, other_rate=0.
                                        ctypes.byref(cnt)))
     k = cnt.value
     return bag[:k], oob[:n - k]
+
+
+_FOREST_KINDS = {"raw": 1, "leaf": 2, "contrib": 3}  # C_API_PREDICT_RAW_SCORE / LEAF_INDEX / CONTRIB
+
+
+def forest_predict(booster, X, kind="raw", start_iteration=0, num_iteration=-1):
+    """Predictions of ``booster`` for the rows of ``X``, a contiguous float32 or float64 GPU
+    tensor ``[n, ncol]``, computed and left on the GPU as a float64 tensor: raw scores
+    ``[n, classes]`` (``kind="raw"``), leaf indices ``[n, trees]`` (``"leaf"``) or SHAP
+    contributions ``[n, classes * (num_features + 1)]`` (``"contrib"``).  Neither rows nor
+    results pass through the host, and any number of rows runs on the device."""
+    torch = _torch()
+    if kind not in _FOREST_KINDS:
+        raise LightGBMError("kind must be one of 'raw', 'leaf', 'contrib', got %r" % (kind,))
+    if not isinstance(X, torch.Tensor) or X.dim() != 2 or X.dtype not in (torch.float32, torch.float64):
+        raise LightGBMError("X must be a 2-d float32 or float64 torch tensor on the GPU")
+    data = _dev_ptr(X, X.dtype, "X")
+    n, ncol = X.shape
+    start = max(0, int(start_iteration))
+    num = int(num_iteration) if num_iteration is not None else -1
+    width = ctypes.c_int64(0)
+    _native_call("LGBM_BoosterCalcNumPredict", booster.handle, ctypes.c_int(1), ctypes.c_int(_FOREST_KINDS[kind]),
+                 ctypes.c_int(start), ctypes.c_int(num), ctypes.byref(width))
+    out = torch.empty((n, width.value), dtype=torch.float64, device=X.device)
+    torch.cuda.synchronize(X.device)
+    _check(_lib().LGBMAMD_OpForestPredict(booster.handle, data, ctypes.c_int(0 if X.dtype == torch.float32 else 1),
+                                       ctypes.c_int64(n), ctypes.c_int32(ncol), ctypes.c_int(_FOREST_KINDS[kind]),
+                                       ctypes.c_int(start), ctypes.c_int(num), _dev_ptr(out, torch.float64, "out"),
+                                       ctypes.c_int64(out.numel())))
+    return out

@@ -2,16 +2,22 @@
 // booster trained with device_type=gpu, or predicted with device_type=gpu): the forest is
 // flattened into node arrays and evaluated by src/device/predict_kernels.hip, one row per
 // thread, with the host predictor's semantics (reference GBDT::PredictRaw / Predict,
-// src/boosting/gbdt_prediction.cpp:13-64); output transforms stay on the host.
+// src/boosting/gbdt_prediction.cpp:13-64); output transforms stay on the host.  Leaf indices
+// come from the same walk and SHAP contributions from the per-leaf path tables of shap_paths.h
+// (src/device/shap_kernels.hip).  Rows go through the device in chunks sized from the free
+// memory, so that a contribution matrix larger than HBM still predicts.
 #include <hip/hip_runtime_api.h>
 #include <omp.h>
 
+#include <atomic>
 #include <cstring>
 #include <vector>
 
 #include "../device/kernels.h"
+#include "shap_paths.h"
 #include "lgbm_amd/boosting.h"
 #include "lgbm_amd/log.h"
+#include "lgbm_amd/tuning.h"
 
 namespace lgbm_amd {
 
@@ -22,6 +28,8 @@ namespace {
     hipError_t e_ = (x);                                                                            \
     if (e_ != hipSuccess) Log::Fatal("HIP error %s at %s:%d: %s", #x, __FILE__, __LINE__, hipGetErrorString(e_)); \
   } while (0)
+
+std::atomic<int64_t> g_device_predictions{0};
 
 // device copies of host vectors, freed together
 struct DeviceBuffers {
@@ -45,90 +53,231 @@ struct DeviceBuffers {
   }
 };
 
-}  // namespace
 
-bool GBDT::PredictDenseOnDevice(const void* data, bool is_double, int64_t nrow, int ncol, bool row_major,
-                                int start_iteration, int num_iteration, bool raw, double* out) {
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return false;
-  if (num_tree_per_iteration_ > dev::kMaxPredClasses || nrow <= 0) return false;
-  InitPredict(start_iteration, num_iteration, false);
-  const int ntpi = num_tree_per_iteration_;
-  const int t0 = start_iteration_for_pred_ * ntpi;
-  const int nt = num_iteration_for_pred_ * ntpi;
-  // flatten the forest (rebuilt per call: trees may have been edited in place)
-  std::vector<int32_t> node_off(nt + 1, 0), leaf_off(nt, 0), feature, left, right;
-  std::vector<int32_t> cat_bound_off(nt, 0), cat_bound, cat_bits_off(nt, 0);
-  std::vector<double> thr, leafv;
-  std::vector<int8_t> dtype;
-  std::vector<uint32_t> cat_bits;
-  for (int i = 0; i < nt; ++i) {
-    const Tree* tr = models_[t0 + i].get();
-    node_off[i] = static_cast<int32_t>(feature.size());
-    leaf_off[i] = static_cast<int32_t>(leafv.size());
-    cat_bound_off[i] = static_cast<int32_t>(cat_bound.size());
-    cat_bits_off[i] = static_cast<int32_t>(cat_bits.size());
-    const int nl = tr->num_leaves();
-    for (int j = 0; j + 1 < nl; ++j) {
-      feature.push_back(tr->split_feature(j));
-      thr.push_back(tr->threshold(j));
-      dtype.push_back(tr->decision_type(j));
-      left.push_back(tr->left_child(j));
-      right.push_back(tr->right_child(j));
+// the forest (and, for contributions, its path tables) of one prediction call on the device
+class DeviceForest {
+ public:
+  // false: the contribution kernel cannot run this forest (the host predicts)
+  bool Upload(const std::vector<const Tree*>& trees, int num_class, int num_features, DevicePredictKind kind,
+              hipStream_t s) {
+    kind_ = kind;
+    flat_.Build(trees);
+    if (kind == DevicePredictKind::Contrib && (!paths_.Build(trees) || !paths_.FitsDevice())) return false;
+    f_.num_class = num_class;
+    f_.num_trees = static_cast<int32_t>(trees.size());
+    f_.node_off = b_.Upload(flat_.node_off, s);
+    f_.leaf_off = b_.Upload(flat_.leaf_off, s);
+    f_.feature = b_.Upload(flat_.feature, s);
+    f_.threshold = b_.Upload(flat_.threshold, s);
+    f_.dtype = b_.Upload(flat_.dtype, s);
+    f_.left = b_.Upload(flat_.left, s);
+    f_.right = b_.Upload(flat_.right, s);
+    f_.leaf_value = b_.Upload(flat_.leaf_value, s);
+    f_.cat_bound_off = b_.Upload(flat_.cat_bound_off, s);
+    f_.cat_bound = b_.Upload(flat_.cat_bound, s);
+    f_.cat_bits_off = b_.Upload(flat_.cat_bits_off, s);
+    f_.cat_bits = b_.Upload(flat_.cat_bits, s);
+    if (kind == DevicePredictKind::Contrib) {
+      a_.num_features = num_features;
+      a_.max_path_len = paths_.max_path_len;
+      a_.mask_words = paths_.mask_words;
+      a_.tree_leaf_off = b_.Upload(paths_.tree_leaf_off, s);
+      a_.leaf_elem_off = b_.Upload(paths_.leaf_elem_off, s);
+      a_.leaf_value = b_.Upload(paths_.leaf_value, s);
+      a_.elem_feature = b_.Upload(paths_.elem_feature, s);
+      a_.elem_zero = b_.Upload(paths_.elem_zero, s);
+      a_.elem_pair_off = b_.Upload(paths_.elem_pair_off, s);
+      a_.pairs = b_.Upload(paths_.pairs, s);
+      a_.expected = b_.Upload(paths_.expected, s);
+      a_.ratio = b_.Upload(paths_.ratio, s);
+      phi_in_lds_ = dev::ShapLdsBytes(a_, true) <= static_cast<size_t>(dev::kShapLdsBytes);
     }
-    for (int j = 0; j < nl; ++j) leafv.push_back(tr->LeafOutput(j));
-    cat_bound.insert(cat_bound.end(), tr->cat_boundaries().begin(), tr->cat_boundaries().end());
-    cat_bits.insert(cat_bits.end(), tr->cat_threshold().begin(), tr->cat_threshold().end());
+    return true;
   }
-  node_off[nt] = static_cast<int32_t>(feature.size());
-  hipStream_t s;
-  HIPCHECK(hipStreamCreateWithFlags(&s, hipStreamNonBlocking));
-  std::vector<double> raw_out(static_cast<size_t>(nrow) * ntpi);
-  {
-    DeviceBuffers b;
-    dev::ForestArgs f{};
-    f.num_trees = nt;
-    f.num_class = ntpi;
+  // doubles of one row's output
+  int64_t OutPerRow() const {
+    if (kind_ == DevicePredictKind::Leaf) return f_.num_trees;
+    if (kind_ == DevicePredictKind::Contrib) return static_cast<int64_t>(f_.num_class) * (a_.num_features + 1);
+    return f_.num_class;
+  }
+  // device bytes a launch over `rows` rows allocates besides its input and output
+  size_t ScratchBytes(int64_t rows) const {
+    if (kind_ != DevicePredictKind::Contrib || phi_in_lds_) return 0;
+    const int tiles = static_cast<int>((rows + dev::kShapLanes - 1) / dev::kShapLanes);
+    return static_cast<size_t>(dev::ShapTileGrid(tiles)) * (a_.num_features + 1) * dev::kShapLanes * sizeof(double);
+  }
+  // rows [0, rows) of d_data (compact: column stride `rows` when column-major) into d_out
+  void Run(const void* d_data, bool is_double, bool row_major, int64_t rows, int ncol, double* d_out,
+           hipStream_t s) {
+    dev::ForestArgs f = f_;
     f.num_cols = ncol;
     f.is_double = is_double ? 1 : 0;
     f.row_major = row_major ? 1 : 0;
-    f.num_rows = nrow;
-    const size_t data_bytes = static_cast<size_t>(nrow) * ncol * (is_double ? 8 : 4);
-    void* d_data = b.Alloc(data_bytes);
-    HIPCHECK(hipMemcpyAsync(d_data, data, data_bytes, hipMemcpyHostToDevice, s));
+    f.num_rows = rows;
     f.data = d_data;
-    f.node_off = b.Upload(node_off, s);
-    f.leaf_off = b.Upload(leaf_off, s);
-    f.feature = b.Upload(feature, s);
-    f.threshold = b.Upload(thr, s);
-    f.dtype = b.Upload(dtype, s);
-    f.left = b.Upload(left, s);
-    f.right = b.Upload(right, s);
-    f.leaf_value = b.Upload(leafv, s);
-    f.cat_bound_off = b.Upload(cat_bound_off, s);
-    f.cat_bound = b.Upload(cat_bound, s);
-    f.cat_bits_off = b.Upload(cat_bits_off, s);
-    f.cat_bits = b.Upload(cat_bits, s);
-    f.out = static_cast<double*>(b.Alloc(raw_out.size() * sizeof(double)));
-    dev::PredictForest(f, s);
-    HIPCHECK(hipMemcpyAsync(raw_out.data(), f.out, raw_out.size() * sizeof(double), hipMemcpyDeviceToHost, s));
-    HIPCHECK(hipStreamSynchronize(s));
+    f.out = d_out;
+    if (kind_ == DevicePredictKind::Leaf) {
+      dev::PredictForestLeaf(f, s);
+    } else if (kind_ == DevicePredictKind::Contrib) {
+      dev::ShapArgs a = a_;
+      a.num_tiles = static_cast<int32_t>((rows + dev::kShapLanes - 1) / dev::kShapLanes);
+      a.out = d_out;
+      if (!phi_in_lds_) {
+        const size_t need = ScratchBytes(rows);
+        if (need > phi_bytes_) {
+          phi_tiles_ = b_.Alloc(need);
+          phi_bytes_ = need;
+        }
+        a.phi_tiles = static_cast<double*>(phi_tiles_);
+      }
+      dev::ShapForest(f, a, s);
+    } else {
+      dev::PredictForest(f, s);
+    }
+    HIPCHECK(hipGetLastError());
+  }
+
+ private:
+  DevicePredictKind kind_ = DevicePredictKind::Raw;
+  FlatForest flat_;
+  ShapPathTables paths_;
+  DeviceBuffers b_;
+  dev::ForestArgs f_{};
+  dev::ShapArgs a_{};
+  bool phi_in_lds_ = true;
+  void* phi_tiles_ = nullptr;
+  size_t phi_bytes_ = 0;
+};
+
+}  // namespace
+
+std::vector<const Tree*> GBDT::PredictWindowTrees(int start_iteration, int num_iteration) {
+  InitPredict(start_iteration, num_iteration, false);
+  const int t0 = start_iteration_for_pred_ * num_tree_per_iteration_;
+  const int nt = num_iteration_for_pred_ * num_tree_per_iteration_;
+  std::vector<const Tree*> trees(nt);
+  for (int i = 0; i < nt; ++i) trees[i] = models_[t0 + i].get();
+  return trees;
+}
+
+bool GBDT::PredictDenseOnDevice(const void* data, bool is_double, int64_t nrow, int ncol, bool row_major,
+                                int start_iteration, int num_iteration, DevicePredictKind kind, double* out) {
+  int ndev = 0;
+  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return false;
+  if (num_tree_per_iteration_ > dev::kMaxPredClasses || nrow <= 0) return false;
+  if (kind != DevicePredictKind::Normal && kind != DevicePredictKind::Raw && ncol <= max_feature_idx_) return false;
+  const int ntpi = num_tree_per_iteration_;
+  // (the forest is rebuilt per call: trees may have been edited in place)
+  const std::vector<const Tree*> trees = PredictWindowTrees(start_iteration, num_iteration);
+  hipStream_t s;
+  HIPCHECK(hipStreamCreateWithFlags(&s, hipStreamNonBlocking));
+  bool ran = false;
+  {
+    DeviceForest forest;
+    if (forest.Upload(trees, ntpi, max_feature_idx_ + 1, kind, s)) {
+      const size_t elem = is_double ? 8 : 4;
+      const int64_t per_out = forest.OutPerRow();
+      // rows per chunk: input, output and the accumulator tiles within most of the free memory
+      size_t free_b = 0, total_b = 0;
+      HIPCHECK(hipMemGetInfo(&free_b, &total_b));
+      const size_t per_row = static_cast<size_t>(ncol) * elem + static_cast<size_t>(per_out) * sizeof(double);
+      const size_t budget = free_b - free_b / 5;
+      const size_t fixed = forest.ScratchBytes(nrow);
+      int64_t chunk = budget > fixed ? static_cast<int64_t>((budget - fixed) / per_row) : 0;
+      chunk = std::max<int64_t>(dev::kShapLanes, chunk / dev::kShapLanes * dev::kShapLanes);
+      const int forced = tuning::Int(tuning::Knob::PredictChunkRows, 0);
+      if (forced > 0) chunk = forced;
+      chunk = std::min(chunk, nrow);
+      DeviceBuffers b;
+      void* d_data = b.Alloc(static_cast<size_t>(chunk) * ncol * elem);
+      double* d_out = static_cast<double*>(b.Alloc(static_cast<size_t>(chunk) * per_out * sizeof(double)));
+      const bool convert = kind == DevicePredictKind::Normal;
+      std::vector<double> raw_out(convert ? static_cast<size_t>(nrow) * per_out : 0);
+      double* host_out = convert ? raw_out.data() : out;
+      for (int64_t r0 = 0; r0 < nrow; r0 += chunk) {
+        const int64_t rows = std::min(chunk, nrow - r0);
+        const char* src = static_cast<const char*>(data);
+        if (row_major) {
+          HIPCHECK(hipMemcpyAsync(d_data, src + static_cast<size_t>(r0) * ncol * elem,
+                                  static_cast<size_t>(rows) * ncol * elem, hipMemcpyHostToDevice, s));
+        } else if (rows == nrow) {
+          HIPCHECK(hipMemcpyAsync(d_data, src, static_cast<size_t>(rows) * ncol * elem, hipMemcpyHostToDevice, s));
+        } else {  // the chunk's rows of every column, compacted to a column stride of `rows`
+          HIPCHECK(hipMemcpy2DAsync(d_data, static_cast<size_t>(rows) * elem, src + static_cast<size_t>(r0) * elem,
+                                    static_cast<size_t>(nrow) * elem, static_cast<size_t>(rows) * elem, ncol,
+                                    hipMemcpyHostToDevice, s));
+        }
+        forest.Run(d_data, is_double, row_major, rows, ncol, d_out, s);
+        HIPCHECK(hipMemcpyAsync(host_out + r0 * per_out, d_out, static_cast<size_t>(rows) * per_out * sizeof(double),
+                                hipMemcpyDeviceToHost, s));
+        HIPCHECK(hipStreamSynchronize(s));
+      }
+      ran = true;
+      ++g_device_predictions;
+      if (convert) {
+#pragma omp parallel for schedule(static)
+        for (int64_t r = 0; r < nrow; ++r) {
+          double* o = out + r * ntpi;
+          std::memcpy(o, raw_out.data() + r * ntpi, sizeof(double) * ntpi);
+          if (average_output_) {
+            for (int k = 0; k < ntpi; ++k) o[k] /= num_iteration_for_pred_;
+          }
+          if (objective_ != nullptr) objective_->ConvertOutput(o, o);
+        }
+      }
+    }
   }
   HIPCHECK(hipStreamDestroy(s));
-  if (raw) {
-    std::memcpy(out, raw_out.data(), raw_out.size() * sizeof(double));
-    return true;
+  return ran;
+}
+
+void GBDT::PredictDeviceBuffers(const void* d_data, bool is_double, int64_t nrow, int ncol, int start_iteration,
+                                int num_iteration, DevicePredictKind kind, double* d_out, int64_t out_len) {
+  if (kind == DevicePredictKind::Normal) Log::Fatal("device buffers are predicted as raw scores, leaf indices or contributions");
+  if (num_tree_per_iteration_ > dev::kMaxPredClasses) {
+    Log::Fatal("forest prediction on the device handles at most %d trees per iteration", dev::kMaxPredClasses);
   }
-#pragma omp parallel for schedule(static)
-  for (int64_t r = 0; r < nrow; ++r) {
-    double* o = out + r * ntpi;
-    std::memcpy(o, raw_out.data() + r * ntpi, sizeof(double) * ntpi);
-    if (average_output_) {
-      for (int k = 0; k < ntpi; ++k) o[k] /= num_iteration_for_pred_;
-    }
-    if (objective_ != nullptr) objective_->ConvertOutput(o, o);
+  if (ncol != max_feature_idx_ + 1) {
+    Log::Fatal("The number of features in data (%d) is not the same as it was in training data (%d).", ncol,
+               max_feature_idx_ + 1);
   }
-  return true;
+  const std::vector<const Tree*> trees = PredictWindowTrees(start_iteration, num_iteration);
+  DeviceForest forest;
+  if (!forest.Upload(trees, num_tree_per_iteration_, max_feature_idx_ + 1, kind, nullptr)) {
+    Log::Fatal("contributions on the device need paths of at most %d distinct features and data counts on every node",
+               dev::kShapMaxPathLen - 1);
+  }
+  if (out_len != nrow * forest.OutPerRow()) {
+    Log::Fatal("output holds %lld doubles, the prediction has %lld", static_cast<long long>(out_len),
+               static_cast<long long>(nrow * forest.OutPerRow()));
+  }
+  if (nrow > 0) forest.Run(d_data, is_double, true, nrow, ncol, d_out, nullptr);
+  HIPCHECK(hipStreamSynchronize(nullptr));
+  ++g_device_predictions;
+}
+
+int64_t GBDT::DevicePredictions() { return g_device_predictions.load(); }
+
+void GBDT::ContribFromPathTables(const double* data, int64_t nrow, int ncol, int start_iteration, int num_iteration,
+                                 double* out) {
+  if (ncol != max_feature_idx_ + 1) Log::Fatal("path tables: %d columns, the model has %d", ncol, max_feature_idx_ + 1);
+  const std::vector<const Tree*> trees = PredictWindowTrees(start_iteration, num_iteration);
+  FlatForest flat;
+  flat.Build(trees);
+  ShapPathTables paths;
+  if (!paths.Build(trees)) Log::Fatal("path tables: a node on a path has data_count 0");
+  dev::ForestArgs f{};
+  flat.HostArgs(&f);
+  f.num_class = num_tree_per_iteration_;
+  f.num_cols = ncol;
+  f.is_double = 1;
+  f.row_major = 1;
+  f.num_rows = nrow;
+  f.data = data;
+  dev::ShapArgs a{};
+  paths.HostArgs(&a);
+  a.num_features = max_feature_idx_ + 1;
+  EvalPathTables(f, a, out);
 }
 
 }  // namespace lgbm_amd

@@ -421,26 +421,63 @@ class Booster {
   }
 
   // dense matrices from a booster trained (or predicted) with device_type=gpu go to the
-  // device forest kernel; single rows, leaf / contrib predictions and early stopping stay on
-  // the host
+  // device forest kernels (scores, leaf indices, SHAP contributions); few rows and early
+  // stopping stay on the host
   bool PredictDenseOnDevice(const void* data, int data_type, int32_t nrow, int32_t ncol, int is_row_major,
                             int predict_type, int start_iteration, int num_iteration, const Config& cfg, double* out,
                             int64_t* out_len) {
-    if (predict_type != C_API_PREDICT_NORMAL && predict_type != C_API_PREDICT_RAW_SCORE) return false;
-    if (cfg.pred_early_stop || nrow < 1024) return false;
+    DevicePredictKind kind;
+    if (!DeviceKindOf(predict_type, &kind)) return false;
+    if (cfg.pred_early_stop || nrow < (kind == DevicePredictKind::Contrib ? kDeviceContribMinRows : 1024)) return false;
     if (data_type != C_API_DTYPE_FLOAT32 && data_type != C_API_DTYPE_FLOAT64) return false;
     if (cfg.device_type != "gpu" && config_.device_type != "gpu") return false;
     const char* e = tuning::Get(tuning::Knob::HostPredict);
     if (e != nullptr && e[0] == '1') return false;
     if (!cfg.predict_disable_shape_check && ncol != boosting_->MaxFeatureIdx() + 1) return false;  // host path reports it
     std::unique_lock<std::shared_mutex> l(mu_);
-    const bool raw = predict_type == C_API_PREDICT_RAW_SCORE;
     if (!boosting_->PredictDenseOnDevice(data, data_type == C_API_DTYPE_FLOAT64, nrow, ncol, is_row_major != 0,
-                                         start_iteration, num_iteration, raw, out)) {
+                                         start_iteration, num_iteration, kind, out)) {
       return false;
     }
-    *out_len = static_cast<int64_t>(nrow) * boosting_->NumPredictOneRow(start_iteration, num_iteration, false, false);
+    *out_len = static_cast<int64_t>(nrow) *
+               boosting_->NumPredictOneRow(start_iteration, num_iteration, kind == DevicePredictKind::Leaf,
+                                           kind == DevicePredictKind::Contrib);
     return true;
+  }
+
+  // raw scores, leaf indices or contributions of a row-major matrix in device memory, into
+  // device memory (lightgbmv1_amd.ops.forest_predict): no row gate, no host round trip
+  void PredictDeviceBuffers(const void* d_data, int data_type, int64_t nrow, int32_t ncol, int predict_type,
+                            int start_iteration, int num_iteration, double* d_out, int64_t out_len) {
+    DevicePredictKind kind;
+    if (!DeviceKindOf(predict_type, &kind) || kind == DevicePredictKind::Normal) {
+      Log::Fatal("forest prediction on device buffers: predict type %d is not raw, leaf or contrib", predict_type);
+    }
+    if (data_type != C_API_DTYPE_FLOAT32 && data_type != C_API_DTYPE_FLOAT64) {
+      Log::Fatal("forest prediction on device buffers: data must be float32 or float64");
+    }
+    std::unique_lock<std::shared_mutex> l(mu_);
+    boosting_->PredictDeviceBuffers(d_data, data_type == C_API_DTYPE_FLOAT64, nrow, ncol, start_iteration,
+                                    num_iteration, kind, d_out, out_len);
+  }
+
+  void ContribFromPathTables(const double* data, int32_t nrow, int32_t ncol, int start_iteration, int num_iteration,
+                             double* out, int64_t* out_len) {
+    std::unique_lock<std::shared_mutex> l(mu_);
+    boosting_->ContribFromPathTables(data, nrow, ncol, start_iteration, num_iteration, out);
+    *out_len = static_cast<int64_t>(nrow) * boosting_->NumPredictOneRow(start_iteration, num_iteration, false, true);
+  }
+
+  // rows from which contributions of a host matrix go to the device (profiles/r07_device_shap.md)
+  static constexpr int kDeviceContribMinRows = 1024;
+  static bool DeviceKindOf(int predict_type, DevicePredictKind* kind) {
+    switch (predict_type) {
+      case C_API_PREDICT_NORMAL: *kind = DevicePredictKind::Normal; return true;
+      case C_API_PREDICT_RAW_SCORE: *kind = DevicePredictKind::Raw; return true;
+      case C_API_PREDICT_LEAF_INDEX: *kind = DevicePredictKind::Leaf; return true;
+      case C_API_PREDICT_CONTRIB: *kind = DevicePredictKind::Contrib; return true;
+      default: return false;
+    }
   }
 
   void PredictFile(const char* data, int header, int predict_type, int start_iteration, int num_iteration,
@@ -1479,6 +1516,30 @@ int LGBM_AMD_BoosterDeviceCheckSplits(BoosterHandle handle, int64_t buffer_len, 
   if (buffer_len >= *out_len) std::memcpy(out_str, rep.c_str(), rep.size() + 1);
   API_END();
 }
+
+int LGBM_AMD_BoosterPathTableContrib(BoosterHandle handle, const double* data, int32_t nrow, int32_t ncol,
+                                     int start_iteration, int num_iteration, int64_t* out_len, double* out_result) {
+  API_BEGIN();
+  static_cast<Booster*>(handle)->ContribFromPathTables(data, nrow, ncol, start_iteration, num_iteration, out_result,
+                                                       out_len);
+  API_END();
+}
+
+int LGBM_AMD_DevicePredictCount(int64_t* out) {
+  API_BEGIN();
+  *out = GBDT::DevicePredictions();
+  API_END();
+}
+
+namespace lgbm_amd {
+// (src/capi/ops_api.cpp: LGBMAMD_OpForestPredict; throws what the op reports)
+void BoosterPredictDeviceBuffers(BoosterHandle handle, const void* d_data, int data_type, int64_t nrow, int32_t ncol,
+                                 int predict_type, int start_iteration, int num_iteration, double* d_out,
+                                 int64_t out_len) {
+  static_cast<Booster*>(handle)->PredictDeviceBuffers(d_data, data_type, nrow, ncol, predict_type, start_iteration,
+                                                      num_iteration, d_out, out_len);
+}
+}  // namespace lgbm_amd
 
 int LGBM_AMD_NetworkReportExternalError(const char* msg) {
   API_BEGIN();

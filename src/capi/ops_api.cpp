@@ -3,7 +3,8 @@
 // point-wise objective gradients (src/device/objective_kernels.hip), validation metrics
 // (src/device/metric_kernels.hip) and the bagging / GOSS row sampler
 // (src/device/sample_kernels.hip) -- callable one at a time so that their numerics can be
-// checked against plain PyTorch references (tests/test_ops.py).
+// checked against plain PyTorch references (tests/test_ops.py); and a booster's forest
+// prediction (scores, leaf indices, SHAP contributions) on a matrix that already is on the device.
 //
 // Objectives and metrics are created from a parameter string exactly as training creates
 // them (reference objective_function.cpp:16-56, metric.cpp:16-63), so the kernels see the
@@ -26,6 +27,13 @@
 #include "lgbm_amd/objective.h"
 
 using namespace lgbm_amd;
+
+namespace lgbm_amd {
+// src/capi/c_api.cpp (the Booster behind a handle lives there)
+void BoosterPredictDeviceBuffers(BoosterHandle handle, const void* d_data, int data_type, int64_t nrow, int32_t ncol,
+                                 int predict_type, int start_iteration, int num_iteration, double* d_out,
+                                 int64_t out_len);
+}  // namespace lgbm_amd
 
 namespace {
 
@@ -87,6 +95,19 @@ void FillMetadata(Metadata* md, const float* label, const float* weight, int32_t
 }  // namespace
 
 LIGHTGBM_C_EXPORT const char* LGBMAMD_OpLastError() { return g_op_error.c_str(); }
+
+// a booster's forest on a row-major float32 / float64 matrix in device memory: raw scores
+// [nrow][classes], leaf indices [nrow][trees] or SHAP contributions [nrow][classes * (F + 1)]
+// (predict_type: C_API_PREDICT_RAW_SCORE / LEAF_INDEX / CONTRIB) into out_len doubles of device
+// memory, with the kernels of LGBM_BoosterPredictForMat's device path
+LIGHTGBM_C_EXPORT int LGBMAMD_OpForestPredict(BoosterHandle handle, const void* d_data, int data_type, int64_t nrow,
+                                              int32_t ncol, int predict_type, int start_iteration, int num_iteration,
+                                              double* d_out, int64_t out_len) {
+  return Guard([&] {
+    BoosterPredictDeviceBuffers(handle, d_data, data_type, nrow, ncol, predict_type, start_iteration, num_iteration,
+                                d_out, out_len);
+  });
+}
 
 // gradients / hessians of a point-wise objective: score [num_class][n] (device, float64),
 // grad / hess [num_class][n] (device, float32); label / weight are host arrays (the objective's

@@ -576,6 +576,42 @@ struct ForestArgs {
   double* out{};              // [num_rows][num_class] raw scores
 };
 void PredictForest(const ForestArgs& f, hipStream_t s);
+// the same walk writing every tree's leaf index: out[num_rows][num_trees] (as doubles, the C
+// API's output type)
+void PredictForestLeaf(const ForestArgs& f, hipStream_t s);
+
+// SHAP contributions of a flattened forest from per-leaf path tables (src/boosting/shap_paths.h;
+// src/device/shap_kernels.hip): one lane per row, a workgroup of kShapLanes rows walks every
+// tree, leaf and path element together.  A workgroup takes at most kShapLdsBytes of LDS (what a
+// launch may ask for without opting in to more): the per-lane path weights ([element][lane]
+// doubles; a leaf's path has at most kShapMaxPathLen elements with the bias element, 60 KiB),
+// the decision mask of the widest tree, and the accumulator tile while it still fits.
+constexpr int kShapLanes = 64;
+constexpr int kShapMaxPathLen = 120;
+constexpr int kShapLdsBytes = 64 * 1024;
+struct ShapArgs {
+  int32_t num_features{};          // F: a row's output has num_class * (F + 1) entries
+  int32_t max_path_len{};          // longest path, bias element included (<= kShapMaxPathLen)
+  int32_t mask_words{};            // 32-bit words of a tree's decision mask (most internal nodes / 32, rounded up)
+  int32_t num_tiles{};             // num_rows / kShapLanes, rounded up
+  const int32_t* tree_leaf_off{};  // [num_trees + 1] leaves of each tree in the tables (none for a single-leaf tree)
+  const int32_t* leaf_elem_off{};  // [leaves + 1] elements of each leaf (the bias element is implicit)
+  const double* leaf_value{};      // [leaves]
+  const int32_t* elem_feature{};   // [elements] real feature index
+  const double* elem_zero{};       // [elements] zero fraction
+  const int32_t* elem_pair_off{};  // [elements + 1] (node, direction) pairs of each element
+  const int32_t* pairs{};          // [pairs] node << 1 | (1: the path goes left)
+  const double* expected{};        // [num_trees] Tree::ExpectedValue()
+  const double* ratio{};           // (D - j) / (D + 1) at ShapRatioOffset(D) + j, D < kShapMaxPathLen
+  double* phi_tiles{};             // null: the tile's accumulator is in LDS; else [grid][F + 1][kShapLanes]
+  double* out{};                   // [num_rows][num_class][F + 1]
+};
+constexpr int ShapRatioOffset(int d) { return d * (d - 1) / 2; }
+// LDS bytes of a workgroup with / without the accumulator tile ((F + 1) rows of kShapLanes + 1)
+size_t ShapLdsBytes(const ShapArgs& a, bool phi_in_lds);
+// workgroups of the launch when the accumulator is a global tile (a.phi_tiles holds that many)
+int ShapTileGrid(int num_tiles);
+void ShapForest(const ForestArgs& f, const ShapArgs& a, hipStream_t s);
 
 // validation metrics on device scores (one model per iteration)
 constexpr int kMetricL2 = 1, kMetricRMSE = 2, kMetricL1 = 3, kMetricBinLogloss = 4, kMetricBinError = 5,
