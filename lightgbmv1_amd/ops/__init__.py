@@ -6,11 +6,16 @@ the kernels can be checked one by one against plain PyTorch references
 (tests/test_ops.py) and reused outside a Booster:
 
 * :func:`gradients` -- point-wise objective gradients / hessians
-  (src/device/objective_kernels.hip; reference src/objective/*.hpp GetGradients)
-* :func:`metric` -- validation metrics incl. AUC (src/device/metric_kernels.hip;
-  reference src/metric/*.hpp Eval)
-* :func:`sample_rows` -- bagging / GOSS row sampling with the reference's per-1024-row
-  generators (src/device/sample_kernels.hip; reference gbdt.cpp:162-243, goss.hpp:103-179)
+  (src/device/objective_kernels.hip; reference src/objective/*.hpp GetGradients) and, given
+  the query sizes (``group``), the listwise ``lambdarank`` / ``rank_xendcg`` gradients with the
+  learner's launch plan (src/device/rank_kernels.hip, src/device/rank_tables.cpp; reference
+  rank_objective.hpp); ``rng_state`` carries XE-NDCG's per-query generators between calls
+* :func:`metric` -- validation metrics incl. AUC and AUC-mu (src/device/metric_kernels.hip;
+  reference src/metric/*.hpp Eval) and, given ``group`` (and ``query_weight``), NDCG / MAP at
+  every ``eval_at`` (reference rank_metric.hpp, map_metric.hpp)
+* :func:`sample_rows` -- bagging, balanced bagging (``label``, ``pos_fraction``,
+  ``neg_fraction``) / GOSS row sampling with the reference's per-1024-row generators
+  (src/device/sample_kernels.hip; reference gbdt.cpp:162-243, goss.hpp:103-179)
 * :func:`forest_predict` -- a trained booster's raw scores, leaf indices or SHAP
   contributions of a matrix that already is on the GPU (src/device/predict_kernels.hip,
   src/device/shap_kernels.hip; reference gbdt_prediction.cpp, Tree::TreeSHAP)
@@ -67,48 +72,84 @@ def _params(params):
     return param_dict_to_str(params).encode("utf-8") if isinstance(params, dict) else str(params).encode("utf-8")
 
 
-def gradients(params, score, label, weight=None):
+def _host_i32(a, name):
+    if a is None:
+        return None, None, 0
+    if type(a).__module__.startswith("torch"):
+        a = a.detach().cpu().numpy()
+    a = np.ascontiguousarray(np.asarray(a, dtype=np.int32).reshape(-1))
+    return a, a.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)), a.shape[0]
+
+
+def gradients(params, score, label, weight=None, group=None, rng_state=None):
     """Gradients and hessians of objective ``params`` (e.g. ``{"objective": "binary"}``).
 
     ``score``: float64 GPU tensor ``[n]`` (multiclass: ``[num_class, n]``).  Returns
-    float32 GPU tensors ``(grad, hess)`` of the same shape."""
+    float32 GPU tensors ``(grad, hess)`` of the same shape.
+
+    ``group`` (query sizes) is needed by ``lambdarank`` and ``rank_xendcg``.  For
+    ``rank_xendcg``, ``rng_state`` is an optional int32 GPU tensor ``[num_queries]`` of the
+    per-query generator states (``Random(objective_seed + q)`` starts at ``objective_seed + q``);
+    it is advanced in place, so two calls on one tensor replay iterations 1 and 2.  Without it
+    every call starts from fresh generators."""
     torch = _torch()
     n = score.shape[-1]
     _dev_ptr(score, torch.float64, "score")
     lab, lab_p = _host_f32(label, n, "label")
     w, w_p = _host_f32(weight, n, "weight")
+    grp, grp_p, nq = _host_i32(group, "group")
+    rng_p = ctypes.c_void_p(0)
+    if rng_state is not None:
+        rng_p = _dev_ptr(rng_state, torch.int32, "rng_state")
+        if rng_state.numel() != nq:
+            raise LightGBMError("rng_state has %d entries, expected one per query (%d)" % (rng_state.numel(), nq))
     grad = torch.empty(score.shape, dtype=torch.float32, device=score.device)
     hess = torch.empty_like(grad)
     torch.cuda.synchronize(score.device)
-    _check(_lib().LGBMAMD_OpGradients(ctypes.c_char_p(_params(params)), lab_p, w_p, ctypes.c_int32(n),
-                                      _dev_ptr(score, torch.float64, "score"), _dev_ptr(grad, torch.float32, "grad"),
-                                      _dev_ptr(hess, torch.float32, "hess")))
-    del lab, w
+    _check(_lib().LGBMAMD_OpGradients(ctypes.c_char_p(_params(params)), lab_p, w_p, ctypes.c_int32(n), grp_p,
+                                      ctypes.c_int32(nq), _dev_ptr(score, torch.float64, "score"),
+                                      _dev_ptr(grad, torch.float32, "grad"), _dev_ptr(hess, torch.float32, "hess"),
+                                      rng_p))
+    del lab, w, grp
     return grad, hess
 
 
-def metric(params, score, label, weight=None):
+def metric(params, score, label, weight=None, group=None, query_weight=None):
     """Value of ``params["metric"]`` on raw GPU scores (float64 ``[n]``, or class-major
     ``[num_class, n]`` for multiclass metrics), with the output transform of
-    ``params["objective"]`` (e.g. sigmoid for binary, softmax for multiclass)."""
+    ``params["objective"]`` (e.g. sigmoid for binary, softmax for multiclass).
+
+    ``ndcg`` and ``map`` need ``group`` (query sizes) and return a list, one value per
+    ``eval_at`` entry; ``query_weight`` (one per query, instead of ``weight``) weighs the
+    queries.  It reaches the metric as the mean of the query's row weights computed in float32,
+    as in training, so it is exact for weights whose multiples up to the query length are
+    float32 numbers."""
     torch = _torch()
     n = score.shape[-1]
     lab, lab_p = _host_f32(label, n, "label")
     w, w_p = _host_f32(weight, n, "weight")
-    out = ctypes.c_double(0.0)
+    grp, grp_p, nq = _host_i32(group, "group")
+    qw, qw_p = _host_f32(query_weight, nq, "query_weight")
+    out = (ctypes.c_double * 64)()
+    cnt = ctypes.c_int32(0)
     torch.cuda.synchronize(score.device)
-    _check(_lib().LGBMAMD_OpMetric(ctypes.c_char_p(_params(params)), lab_p, w_p, ctypes.c_int32(n),
-                                   _dev_ptr(score, torch.float64, "score"), ctypes.byref(out)))
-    del lab, w
-    return out.value
+    _check(_lib().LGBMAMD_OpMetric(ctypes.c_char_p(_params(params)), lab_p, w_p, ctypes.c_int32(n), grp_p,
+                                   ctypes.c_int32(nq), qw_p, _dev_ptr(score, torch.float64, "score"), out,
+                                   ctypes.c_int32(64), ctypes.byref(cnt)))
+    del lab, w, grp, qw
+    if group is not None:
+        return [out[i] for i in range(cnt.value)]
+    return out[0]
 
 
 def sample_rows(n, fraction=1.0, seed=3, goss=False, top_rate=0.2, other_rate=0.1, grad=None, hess=None,
-                device="cuda"):
+                device="cuda", label=None, pos_fraction=1.0, neg_fraction=1.0):
     """One bagging (``goss=False``: keep ``fraction`` of every 1024-row block) or GOSS draw
     with fresh generators ``Random(seed + block)``.  Returns ``(bag, oob)`` int32 GPU
     tensors: in-bag rows ascending and the out-of-bag rows.  GOSS needs float32 GPU
-    ``grad`` / ``hess`` (``[n]`` or ``[num_class, n]``) and rescales the sampled rows in place."""
+    ``grad`` / ``hess`` (``[n]`` or ``[num_class, n]``) and rescales the sampled rows in place.
+    With ``label`` (host, ``[n]``) bagging is balanced: rows of ``label > 0`` are kept with
+    ``pos_fraction``, the others with ``neg_fraction``."""
     torch = _torch()
     bag = torch.empty(n, dtype=torch.int32, device=device)
     oob = torch.empty(n, dtype=torch.int32, device=device)
@@ -120,13 +161,16 @@ def sample_rows(n, fraction=1.0, seed=3, goss=False, top_rate=0.2, other_rate=0.
         num_class = 1 if grad.dim() == 1 else grad.shape[0]
         gp = _dev_ptr(grad, torch.float32, "grad")
         hp = _dev_ptr(hess, torch.float32, "hess")
+    lab, lab_p = _host_f32(label, n, "label")
     cnt = ctypes.c_int32(0)
     torch.cuda.synchronize(bag.device)
     _check(_lib().LGBMAMD_OpSampleRows(ctypes.c_int64(n), ctypes.c_int32(seed), ctypes.c_int32(1 if goss else 0),
                                        ctypes.c_int32(num_class), ctypes.c_double(fraction),
-                                       ctypes.c_double(top_rate), ctypes.c_double(other_rate), gp, hp,
+                                       ctypes.c_double(top_rate), ctypes.c_double(other_rate), gp, hp, lab_p,
+                                       ctypes.c_double(pos_fraction), ctypes.c_double(neg_fraction),
                                        _dev_ptr(bag, torch.int32, "bag"), _dev_ptr(oob, torch.int32, "oob"),
                                        ctypes.byref(cnt)))
+    del lab
     k = cnt.value
     return bag[:k], oob[:n - k]
 

@@ -2,9 +2,11 @@
 // for lightgbmv1_amd.ops: the same HIP kernels the device learner runs each iteration --
 // point-wise objective gradients (src/device/objective_kernels.hip), validation metrics
 // (src/device/metric_kernels.hip) and the bagging / GOSS row sampler
-// (src/device/sample_kernels.hip) -- callable one at a time so that their numerics can be
-// checked against plain PyTorch references (tests/test_ops.py); and a booster's forest
-// prediction (scores, leaf indices, SHAP contributions) on a matrix that already is on the device.
+// (src/device/sample_kernels.hip), and with query sizes the listwise ranking gradients
+// (src/device/rank_kernels.hip) and the NDCG / MAP metrics -- callable one at a time so that
+// their numerics can be checked against plain PyTorch / NumPy references (tests/test_ops.py,
+// tests/test_rank_ops.py); and a booster's forest prediction (scores, leaf indices, SHAP
+// contributions) on a matrix that already is on the device.
 //
 // Objectives and metrics are created from a parameter string exactly as training creates
 // them (reference objective_function.cpp:16-56, metric.cpp:16-63), so the kernels see the
@@ -18,6 +20,7 @@
 #include <vector>
 
 #include "../device/kernels.h"
+#include "../device/rank_tables.h"
 #include "lgbm_amd/c_api.h"
 #include "lgbm_amd/config.h"
 #include "lgbm_amd/dataset.h"
@@ -86,10 +89,62 @@ Config ParseConfig(const char* params) {
   return c;
 }
 
-void FillMetadata(Metadata* md, const float* label, const float* weight, int32_t n) {
+void FillMetadata(Metadata* md, const float* label, const float* weight, int32_t n, const int32_t* group = nullptr,
+                  int32_t num_group = 0) {
   md->Init(n, weight != nullptr, false);
   md->SetLabel(label, n);
   if (weight != nullptr) md->SetWeights(weight, n);
+  if (group != nullptr && num_group > 0) md->SetQuery(group, num_group);
+}
+
+// listwise gradients (LambdaRank-NDCG / XE-NDCG) with the learner's launch plan
+// (dev::UploadRankTables) over the op's own scratch; d_rng: the caller's xendcg generator
+// states (advanced in place), or null for the objective's fresh ones
+void RankGradientsOp(const DeviceGradSpec& spec, int32_t n, const double* d_score, float* d_grad, float* d_hess,
+                     uint32_t* d_rng) {
+  if (spec.rank.query_boundaries == nullptr || spec.rank.num_queries <= 0) {
+    Log::Fatal("op gradients: a ranking objective needs the query sizes (group)");
+  }
+  Scratch sc;
+  const dev::RankTables rt = dev::UploadRankTables(spec.rank, spec.kind, n, [&sc](size_t bytes) -> void* {
+    return sc.Alloc<char>(bytes);
+  });
+  dev::PrepareRankKernels(dev::RankMaxLds());
+  dev::RankArgs ra{};
+  tuning::PoisonArgs(&ra);  // (every field set below)
+  ra.kind = spec.kind == DeviceGradKind::Lambdarank ? dev::kRankKindLambdarank : dev::kRankKindXendcg;
+  ra.num_queries = spec.rank.num_queries;
+  ra.qb = rt.qb;
+  ra.label = sc.Upload(spec.label, n);
+  ra.weights = sc.Upload(spec.weights, n);
+  ra.score = d_score;
+  ra.grad = d_grad;
+  ra.hess = d_hess;
+  ra.inv_max_dcg = rt.inv_max_dcg;
+  ra.label_gain = rt.label_gain;
+  ra.discount = rt.discount;
+  ra.sigmoid = spec.rank.sigmoid;
+  ra.sig_min = spec.rank.sig_min;
+  ra.sig_max = spec.rank.sig_max;
+  ra.sig_factor = spec.rank.sig_factor;
+  ra.sig_table = rt.sig_table;
+  ra.norm = spec.rank.norm ? 1 : 0;
+  ra.rng = d_rng != nullptr ? d_rng : rt.rng;
+  ra.big_q = rt.big_q;
+  ra.num_big = rt.num_big;
+  ra.big_d0 = rt.big_d0;
+  ra.big_d1 = rt.big_d1;
+  ra.big_dh = rt.big_dh;
+  ra.big_f = rt.big_f;
+  ra.big_i0 = rt.big_i0;
+  ra.big_i1 = rt.big_i1;
+  ra.big_i2 = rt.big_i2;
+  ra.max_docs = rt.max_docs;
+  ra.pair_buf = rt.pairs;
+  ra.pair_off = rt.pair_off;
+  dev::RankGradients(ra, nullptr);
+  OPCHECK(hipGetLastError());
+  OPCHECK(hipDeviceSynchronize());
 }
 
 }  // namespace
@@ -109,22 +164,28 @@ LIGHTGBM_C_EXPORT int LGBMAMD_OpForestPredict(BoosterHandle handle, const void* 
   });
 }
 
-// gradients / hessians of a point-wise objective: score [num_class][n] (device, float64),
-// grad / hess [num_class][n] (device, float32); label / weight are host arrays (the objective's
-// Init reads them: label checks, MAPE weights, class counts)
+// gradients / hessians of an objective: score [num_class][n] (device, float64), grad / hess
+// [num_class][n] (device, float32); label / weight / group are host arrays (the objective's
+// Init reads them: label checks, MAPE weights, class counts, query boundaries).  The listwise
+// objectives (lambdarank, rank_xendcg) need group, the num_group query sizes; d_rng (device,
+// [num_group], or null) holds XE-NDCG's per-query generator states and is advanced in place
 LIGHTGBM_C_EXPORT int LGBMAMD_OpGradients(const char* params, const float* label, const float* weight, int32_t n,
-                                          const double* d_score, float* d_grad, float* d_hess) {
+                                          const int32_t* group, int32_t num_group, const double* d_score,
+                                          float* d_grad, float* d_hess, uint32_t* d_rng) {
   return Guard([&] {
     Config c = ParseConfig(params);
     std::unique_ptr<ObjectiveFunction> obj(ObjectiveFunction::CreateObjectiveFunction(c.objective, c));
     if (!obj) Log::Fatal("op gradients: no objective '%s'", c.objective.c_str());
     Metadata md;
-    FillMetadata(&md, label, weight, n);
+    FillMetadata(&md, label, weight, n, group, num_group);
     obj->Init(md, n);
     const DeviceGradSpec spec = obj->DeviceSpec();
-    if (spec.kind == DeviceGradKind::None || spec.kind == DeviceGradKind::Lambdarank ||
-        spec.kind == DeviceGradKind::RankXendcg || spec.kind == DeviceGradKind::MulticlassOVA) {
-      Log::Fatal("op gradients: objective '%s' has no point-wise device kernel", c.objective.c_str());
+    if (spec.kind == DeviceGradKind::Lambdarank || spec.kind == DeviceGradKind::RankXendcg) {
+      RankGradientsOp(spec, n, d_score, d_grad, d_hess, d_rng);
+      return;
+    }
+    if (spec.kind == DeviceGradKind::None || spec.kind == DeviceGradKind::MulticlassOVA) {
+      Log::Fatal("op gradients: objective '%s' has no device kernel", c.objective.c_str());
     }
     Scratch sc;
     dev::GradArgs g{};
@@ -155,9 +216,14 @@ LIGHTGBM_C_EXPORT int LGBMAMD_OpGradients(const char* params, const float* label
 }
 
 // a validation metric of raw scores (device, float64, one model per iteration); params
-// name the metric and the objective whose output transform applies
+// name the metric and the objective whose output transform applies.  NDCG / MAP need group (the
+// num_group query sizes) and give one value per eval_at entry; query_weight ([num_group], or
+// null) reaches them as the reference derives query weights: the float mean of the query's row
+// weights, every row of a query carrying the query's weight.  out receives *out_count <= out_cap
+// values
 LIGHTGBM_C_EXPORT int LGBMAMD_OpMetric(const char* params, const float* label, const float* weight, int32_t n,
-                                       const double* d_score, double* out) {
+                                       const int32_t* group, int32_t num_group, const float* query_weight,
+                                       const double* d_score, double* out, int32_t out_cap, int32_t* out_count) {
   return Guard([&] {
     Config c = ParseConfig(params);
     if (c.metric.empty()) Log::Fatal("op metric: no metric given");
@@ -167,20 +233,44 @@ LIGHTGBM_C_EXPORT int LGBMAMD_OpMetric(const char* params, const float* label, c
     if (!c.objective.empty() && c.objective != "none") {
       obj.reset(ObjectiveFunction::CreateObjectiveFunction(c.objective, c));
     }
+    std::vector<float> row_qw;
+    if (query_weight != nullptr) {
+      if (group == nullptr || weight != nullptr) Log::Fatal("op metric: query weights need group and no row weights");
+      for (int32_t q = 0; q < num_group; ++q) {
+        row_qw.insert(row_qw.end(), static_cast<size_t>(group[q]), query_weight[q]);
+      }
+      if (static_cast<int64_t>(row_qw.size()) != n) Log::Fatal("op metric: the query sizes do not add up to the rows");
+      weight = row_qw.data();
+    }
     Metadata md;
-    FillMetadata(&md, label, weight, n);
+    FillMetadata(&md, label, weight, n, group, num_group);
     m->Init(md, n);
     if (obj) obj->Init(md, n);
     const DeviceMetricSpec spec = m->DeviceSpec(obj.get());
     if (spec.kind == 0) Log::Fatal("op metric: '%s' has no device kernel for this objective", c.metric[0].c_str());
+    auto give = [&](const std::vector<double>& v) {
+      if (static_cast<int32_t>(v.size()) > out_cap) {
+        Log::Fatal("op metric: %d values, room for %d", static_cast<int>(v.size()), out_cap);
+      }
+      for (size_t i = 0; i < v.size(); ++i) out[i] = v[i];
+      *out_count = static_cast<int32_t>(v.size());
+    };
     bool negative_weight = false;
     for (int32_t i = 0; weight != nullptr && i < n && !negative_weight; ++i) negative_weight = weight[i] < 0.0f;
     if (spec.kind == dev::kMetricAUC && negative_weight) {
       // the device AUC carries the class in the weight's sign: evaluate these rows on the host
       std::vector<double> hs(static_cast<size_t>(std::max(0, n)));
       OPCHECK(hipMemcpy(hs.data(), d_score, sizeof(double) * hs.size(), hipMemcpyDeviceToHost));
-      *out = m->Eval(hs.data(), obj.get())[0];
+      give({m->Eval(hs.data(), obj.get())[0]});
       return;
+    }
+    const bool query = spec.kind == dev::kMetricNDCG || spec.kind == dev::kMetricMAP;
+    if (query && (spec.qb == nullptr || spec.nq <= 0 || spec.eval_at.empty())) {
+      Log::Fatal("op metric: query metrics need the query sizes (group)");
+    }
+    if (query && spec.max_query_docs > tuning::kQueryMetricDeviceMaxDocs) {
+      Log::Fatal("op metric: a query of %d documents is over the device kernel's %d",
+                 static_cast<int>(spec.max_query_docs), tuning::kQueryMetricDeviceMaxDocs);
     }
     Scratch sc;
     dev::MetricArgs a{};
@@ -194,23 +284,35 @@ LIGHTGBM_C_EXPORT int LGBMAMD_OpMetric(const char* params, const float* label, c
     a.score = d_score;
     a.label = sc.Upload(spec.label, n);
     a.weights = sc.Upload(spec.weights, n);
-    a.scratch = sc.Alloc<char>(dev::MetricScratchBytes(n));
-    if (spec.kind == dev::kMetricNDCG || spec.kind == dev::kMetricMAP) Log::Fatal("op metric: query metrics need queries");
-    a.out = sc.Alloc<double>(2);
+    if (query) {
+      const dev::MetricQueryInputs qi = dev::UploadMetricQueryInputs(spec, n, [&sc](size_t bytes) -> void* {
+        return sc.Alloc<char>(bytes);
+      });
+      dev::SetMetricQueryArgs(&a, spec, qi);
+    } else {
+      // (AUC-mu: the class weight matrix)
+      if (spec.kind == dev::kMetricAucMu) a.qconst = sc.Upload(spec.qconst.data(), spec.qconst.size());
+      a.scratch = sc.Alloc<char>(dev::MetricScratchBytes(n));
+    }
+    const size_t nout = static_cast<size_t>(std::max(2, spec.nout));
+    a.out = sc.Alloc<double>(nout);
     dev::EvalMetric(a, nullptr);
     OPCHECK(hipGetLastError());
-    std::vector<double> h(2, 0.0);
-    OPCHECK(hipMemcpy(h.data(), a.out, sizeof(double) * 2, hipMemcpyDeviceToHost));
-    *out = m->FinishDevice(h)[0];
+    std::vector<double> h(nout, 0.0);
+    OPCHECK(hipMemcpy(h.data(), a.out, sizeof(double) * nout, hipMemcpyDeviceToHost));
+    give(m->FinishDevice(h));
   });
 }
 
 // one bagging (goss = 0) or GOSS (goss = 1) draw with fresh generators Random(seed + block):
 // d_bag receives the in-bag rows ascending, d_oob the others; GOSS rescales the sampled
-// small-gradient rows of d_grad / d_hess ([num_class][n]) in place
+// small-gradient rows of d_grad / d_hess ([num_class][n]) in place.  label (host, [n], or null):
+// balanced bagging, rows of label > 0 kept with pos_fraction and the others with neg_fraction
 LIGHTGBM_C_EXPORT int LGBMAMD_OpSampleRows(int64_t n, int32_t seed, int32_t goss, int32_t num_class,
                                            double fraction, double top_rate, double other_rate, float* d_grad,
-                                           float* d_hess, int32_t* d_bag, int32_t* d_oob, int32_t* out_count) {
+                                           float* d_hess, const float* label, double pos_fraction,
+                                           double neg_fraction, int32_t* d_bag, int32_t* d_oob,
+                                           int32_t* out_count) {
   return Guard([&] {
     Scratch sc;
     const int64_t nb = dev::SampleBlocks(n);
@@ -221,13 +323,14 @@ LIGHTGBM_C_EXPORT int LGBMAMD_OpSampleRows(int64_t n, int32_t seed, int32_t goss
     s.num_data = n;
     s.num_blocks = nb;
     s.goss = goss;
-    s.balanced = 0;
+    s.balanced = label != nullptr ? 1 : 0;
     s.num_class = num_class;
     s.fraction = fraction;
-    s.pos_fraction = s.neg_fraction = 1.0;
+    s.pos_fraction = pos_fraction;
+    s.neg_fraction = neg_fraction;
     s.top_rate = top_rate;
     s.other_rate = other_rate;
-    s.label = nullptr;
+    s.label = sc.Upload(label, static_cast<size_t>(n));
     s.grad = d_grad;
     s.hess = d_hess;
     s.rng = sc.Upload(st.data(), st.size());

@@ -194,7 +194,6 @@ template void LaunchReduce<1>(const KArgs&, hipStream_t);
 
 void PrepareSplitKernels(int max_lds);
 void PrepareRoundKernels(int max_lds);
-void PrepareRankKernels(int max_lds);
 
 // dynamic LDS above 64 KiB must be enabled per kernel (outside any graph capture)
 void PrepareKernels() {

@@ -525,6 +525,10 @@ struct RankArgs {
 };
 void RankGradients(const RankArgs& ra, hipStream_t s);
 size_t RankLdsBytes(int max_docs);  // k_lambdarank's dynamic LDS for queries of up to max_docs documents
+// allows k_lambdarank dynamic LDS up to max_lds bytes (above 64 KiB it must be enabled once per
+// process: PrepareKernels does it for the learner); RankMaxLds: the device's per-workgroup limit
+void PrepareRankKernels(int max_lds);
+int RankMaxLds();
 
 // row sampling (bagging / GOSS) with the reference's per-1024-row generators: in-bag rows
 // (ascending) then out-of-bag rows, and the in-bag count, written on the device

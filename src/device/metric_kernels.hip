@@ -265,10 +265,14 @@ __device__ void QueryMetricBody(const MetricArgs& m, int q, double* partials, do
   for (int kk = 0; kk < m.nk; ++kk) {
     const int k = min(m.eval_at[kk], cnt);
     double v = 0.0;
+    double wk = w;
     if (m.kind == kMetricNDCG) {
       const double inv = m.qconst[static_cast<int64_t>(q) * m.nk + kk];
       if (m.qconst[static_cast<int64_t>(q) * m.nk] <= 0.0) {
-        v = threadIdx.x == 0 ? 1.0 : 0.0;  // no relevant document: NDCG 1
+        // no relevant document: NDCG 1, added as it is also when the queries carry weights
+        // (reference rank_metric.hpp:118-121)
+        v = threadIdx.x == 0 ? 1.0 : 0.0;
+        wk = 1.0;
       } else {
         for (int i = threadIdx.x; i < cnt; i += NT) {
           if (s_pos[i] < k) v += m.label_gain[s_label[i]] * m.discount[s_pos[i]];
@@ -287,7 +291,7 @@ __device__ void QueryMetricBody(const MetricArgs& m, int q, double* partials, do
       v = npos > 0 ? v / min(npos, k) : (threadIdx.x == 0 ? 1.0 : 0.0);
     }
     const double t = QBlockSum<NT>(v, red);
-    if (threadIdx.x == 0) partials[static_cast<int64_t>(q) * m.nk + kk] = t * w;
+    if (threadIdx.x == 0) partials[static_cast<int64_t>(q) * m.nk + kk] = t * wk;
   }
 }
 

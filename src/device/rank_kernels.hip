@@ -309,6 +309,16 @@ void PrepareRankKernels(int max_lds) {
 
 size_t RankLdsBytes(int max_docs) { return RankLds(max_docs); }
 
+int RankMaxLds() {
+  int dev = 0, v = 0;
+  if (hipGetDevice(&dev) != hipSuccess ||
+      hipDeviceGetAttribute(&v, hipDeviceAttributeMaxSharedMemoryPerBlock, dev) != hipSuccess) {
+    (void)hipGetLastError();
+    return 65536;
+  }
+  return v;
+}
+
 void RankGradients(const RankArgs& ra, hipStream_t s) {
   if (ra.num_queries <= 0) return;
   if (ra.kind == kRankKindLambdarank) {

@@ -490,7 +490,9 @@ class NDCGMetric : public QueryMetricBase {
       for (data_size_t q = 0; q < nq_; ++q) {
         const double w = qw_ ? qw_[q] : 1.0;
         if (inv_max_[q][0] <= 0.0) {
-          for (size_t j = 0; j < K; ++j) buf[tid][j] += 1.0 * w;
+          // no relevant document: NDCG 1, added as it is also when the queries carry weights
+          // (reference rank_metric.hpp:118-121)
+          for (size_t j = 0; j < K; ++j) buf[tid][j] += 1.0;
         } else {
           DCG::DCGAt(eval_at_, label_ + qb_[q], score + qb_[q], qb_[q + 1] - qb_[q], &tmp);
           for (size_t j = 0; j < K; ++j) buf[tid][j] += tmp[j] * inv_max_[q][j] * w;

@@ -99,31 +99,9 @@ bool GPUTreeLearner::ValidEval(int slot, const DeviceMetricSpec& spec, std::vect
     // the metric's query inputs, uploaded on its first evaluation
     auto it = vs.queries.find(spec.key);
     if (it == vs.queries.end()) {
-      ValidSet::QueryInputs qi;
-      std::vector<int32_t> qb(spec.qb, spec.qb + spec.nq + 1);
-      qi.qb = static_cast<int32_t*>(upload(qb.data(), sizeof(int32_t) * qb.size()));
-      if (spec.qw != nullptr) qi.qw = static_cast<float*>(upload(spec.qw, sizeof(float) * spec.nq));
-      std::vector<int32_t> at(spec.eval_at.begin(), spec.eval_at.end());
-      qi.eval_at = static_cast<int32_t*>(upload(at.data(), sizeof(int32_t) * at.size()));
-      qi.qconst = static_cast<double*>(upload(spec.qconst.data(), sizeof(double) * spec.qconst.size()));
-      qi.label_gain = static_cast<double*>(upload(spec.label_gain.data(), sizeof(double) * spec.label_gain.size()));
-      qi.discount = static_cast<double*>(upload(spec.discount.data(), sizeof(double) * spec.discount.size()));
-      qi.big = spec.max_query_docs > dev::kRankMaxDocs;
-      qi.scratch = dev_alloc(dev::MetricScratchBytes(qi.big ? vs.num_data : 0,
-                                                     static_cast<int64_t>(spec.nq) * spec.eval_at.size()));
-      it = vs.queries.emplace(spec.key, qi).first;
+      it = vs.queries.emplace(spec.key, dev::UploadMetricQueryInputs(spec, vs.num_data, dev_alloc)).first;
     }
-    const ValidSet::QueryInputs& qi = it->second;
-    m.nq = spec.nq;
-    m.nk = static_cast<int32_t>(spec.eval_at.size());
-    m.qb = qi.qb;
-    m.qw = qi.qw;
-    m.eval_at = qi.eval_at;
-    m.qconst = qi.qconst;
-    m.label_gain = qi.label_gain;
-    m.discount = qi.discount;
-    m.scratch = qi.scratch;
-    m.big = qi.big ? 1 : 0;
+    dev::SetMetricQueryArgs(&m, spec, it->second);
   } else {
     if (aucmu) {  // the class weight matrix, uploaded on the metric's first evaluation
       auto it = vs.queries.find(spec.key);
@@ -466,37 +444,39 @@ bool GPUTreeLearner::ComputeGradients(const DeviceGradSpec& spec, int ntpi) {
   last_grad_fusable_ = false;
   if (listwise) {
     UploadRankTables(spec.rank, spec.kind);
+    const dev::RankTables& rt = rank_tables_;
     dev::RankArgs ra{};
+    tuning::PoisonArgs(&ra);  // (every field set below)
     ra.kind = spec.kind == DeviceGradKind::Lambdarank ? dev::kRankKindLambdarank : dev::kRankKindXendcg;
     ra.num_queries = spec.rank.num_queries;
-    ra.qb = d_qb_;
+    ra.qb = rt.qb;
     ra.label = d_label_;
     ra.weights = spec.weights != nullptr ? d_weights_ : nullptr;
     ra.score = d_score_;
     ra.grad = d_grad_;
     ra.hess = d_hess_;
-    ra.inv_max_dcg = d_inv_max_dcg_;
-    ra.label_gain = d_label_gain_;
-    ra.discount = d_discount_;
+    ra.inv_max_dcg = rt.inv_max_dcg;
+    ra.label_gain = rt.label_gain;
+    ra.discount = rt.discount;
     ra.sigmoid = spec.rank.sigmoid;
     ra.sig_min = spec.rank.sig_min;
     ra.sig_max = spec.rank.sig_max;
     ra.sig_factor = spec.rank.sig_factor;
-    ra.sig_table = d_sig_table_;
-    ra.big_q = d_rank_big_q_;
-    ra.num_big = rank_num_big_;
-    ra.big_d0 = d_rank_big_d0_;
-    ra.big_d1 = d_rank_big_d1_;
-    ra.big_dh = d_rank_big_dh_;
-    ra.max_docs = rank_max_docs_;
-    ra.pair_buf = d_rank_pairs_;
-    ra.pair_off = d_rank_pair_off_;
-    ra.big_f = d_rank_big_f_;
-    ra.big_i0 = d_rank_big_i0_;
-    ra.big_i1 = d_rank_big_i1_;
-    ra.big_i2 = d_rank_big_i2_;
+    ra.sig_table = rt.sig_table;
     ra.norm = spec.rank.norm ? 1 : 0;
-    ra.rng = d_rank_rng_;
+    ra.rng = rt.rng;
+    ra.big_q = rt.big_q;
+    ra.num_big = rt.num_big;
+    ra.big_d0 = rt.big_d0;
+    ra.big_d1 = rt.big_d1;
+    ra.big_dh = rt.big_dh;
+    ra.big_f = rt.big_f;
+    ra.big_i0 = rt.big_i0;
+    ra.big_i1 = rt.big_i1;
+    ra.big_i2 = rt.big_i2;
+    ra.max_docs = rt.max_docs;
+    ra.pair_buf = rt.pairs;
+    ra.pair_off = rt.pair_off;
     dev::RankGradients(ra, stream_);
     HIPCHECK(hipGetLastError());  // (a failed launch would leave last iteration's gradients)
     gh_fresh_ = false;
@@ -553,90 +533,12 @@ bool GPUTreeLearner::ComputeGradients(const DeviceGradSpec& spec, int ntpi) {
   return true;
 }
 
-// query boundaries, 1 / max DCG, label gains and position discounts (lambdarank) or the
-// per-query generators (xendcg; from here on they advance on the device)
+// the listwise objective's query tables and launch plan (src/device/rank_tables.cpp, shared with
+// the stand-alone gradient op), uploaded once per dataset into buffers this learner owns
 void GPUTreeLearner::UploadRankTables(const DeviceRankSpec& r, DeviceGradKind kind) {
   if (uploaded_qb_src_ == r.query_boundaries) return;
-  const size_t nq = static_cast<size_t>(r.num_queries);
-  d_qb_ = Alloc<int32_t>(nq + 1);
-  HIPCHECK(hipMemcpy(d_qb_, r.query_boundaries, sizeof(int32_t) * (nq + 1), hipMemcpyHostToDevice));
-  if (kind == DeviceGradKind::Lambdarank) {
-    d_inv_max_dcg_ = Alloc<double>(nq);
-    HIPCHECK(hipMemcpy(d_inv_max_dcg_, r.inv_max_dcg, sizeof(double) * nq, hipMemcpyHostToDevice));
-    d_label_gain_ = Alloc<double>(r.num_label_gain);
-    HIPCHECK(hipMemcpy(d_label_gain_, r.label_gain, sizeof(double) * r.num_label_gain, hipMemcpyHostToDevice));
-    std::vector<double> disc(std::max<data_size_t>(1, r.max_query_docs));
-    for (size_t i = 0; i < disc.size(); ++i) disc[i] = DCG::Discount(static_cast<data_size_t>(i));
-    d_discount_ = Alloc<double>(disc.size());
-    HIPCHECK(hipMemcpy(d_discount_, disc.data(), sizeof(double) * disc.size(), hipMemcpyHostToDevice));
-    if (r.sig_table == nullptr || r.sig_bins != dev::kRankSigmoidBins) {
-      Log::Fatal("device lambdarank: the objective's sigmoid table (%lld entries) is not the device's (%d)",
-                 static_cast<long long>(r.sig_bins), dev::kRankSigmoidBins);
-    }
-    d_sig_table_ = Alloc<double>(static_cast<size_t>(r.sig_bins));
-    HIPCHECK(hipMemcpy(d_sig_table_, r.sig_table, sizeof(double) * r.sig_bins, hipMemcpyHostToDevice));
-  } else {
-    d_rank_rng_ = Alloc<uint32_t>(nq);
-    HIPCHECK(hipMemcpy(d_rank_rng_, r.rng_states, sizeof(uint32_t) * nq, hipMemcpyHostToDevice));
-  }
-  // queries longer than the LDS staging: one 1024-thread workgroup each over a global scratch;
-  // the others' LDS is sized to the longest of them.  Lambdarank: the pair scratch of every
-  // LDS-staged query (cnt^2 float pairs each), within a memory budget
-  std::vector<int32_t> big;
-  std::vector<int64_t> pair_off(nq, 0);
-  int64_t pair_total = 0;
-  rank_max_docs_ = 1;
-  for (size_t q = 0; q < nq; ++q) {
-    const int64_t cnt = r.query_boundaries[q + 1] - r.query_boundaries[q];
-    if (cnt > dev::kRankMaxDocs) {
-      big.push_back(static_cast<int32_t>(q));
-      continue;
-    }
-    rank_max_docs_ = std::max<int32_t>(rank_max_docs_, static_cast<int32_t>(cnt));
-    pair_off[q] = pair_total;
-    pair_total += cnt * cnt;
-  }
-  d_rank_pairs_ = nullptr;
-  d_rank_pair_off_ = nullptr;
-  // budget: a share of the free memory (the histograms and round buffers are already resident),
-  // capped; LGBM_AMD_RANK_PAIR_MB overrides it
-  int64_t pair_budget = int64_t{tuning::kRankPairCapMb} << 20;
-  size_t free_b = 0, total_b = 0;
-  if (hipMemGetInfo(&free_b, &total_b) == hipSuccess) {
-    pair_budget = std::min<int64_t>(pair_budget, static_cast<int64_t>(tuning::kRankPairFreeShare * free_b));
-  } else {
-    (void)hipGetLastError();
-  }
-  pair_budget = static_cast<int64_t>(tuning::Int(tuning::Knob::RankPairMb, static_cast<int>(pair_budget >> 20))) << 20;
-  const int64_t pair_bytes = pair_total * static_cast<int64_t>(sizeof(float2));
-  if (kind == DeviceGradKind::Lambdarank && pair_total > 0 && pair_bytes > pair_budget) {
-    Log::Info("device lambdarank: pair scratch of %.1f MiB is over its %.1f MiB budget; each pair is evaluated "
-              "from both of its documents", pair_bytes / 1048576.0, pair_budget / 1048576.0);
-  }
-  if (kind == DeviceGradKind::Lambdarank && pair_total > 0 && pair_bytes <= pair_budget) {
-    d_rank_pairs_ = Alloc<float2>(static_cast<size_t>(pair_total));
-    d_rank_pair_off_ = Alloc<int64_t>(nq);
-    HIPCHECK(hipMemcpy(d_rank_pair_off_, pair_off.data(), sizeof(int64_t) * nq, hipMemcpyHostToDevice));
-  }
-  rank_num_big_ = static_cast<int32_t>(big.size());
-  d_rank_big_q_ = nullptr;
-  d_rank_big_d0_ = d_rank_big_d1_ = d_rank_big_dh_ = nullptr;
-  d_rank_big_f_ = nullptr;
-  d_rank_big_i0_ = d_rank_big_i1_ = d_rank_big_i2_ = nullptr;
-  if (!big.empty()) {
-    const size_t n = static_cast<size_t>(num_data_);
-    d_rank_big_q_ = Alloc<int32_t>(big.size());
-    HIPCHECK(hipMemcpy(d_rank_big_q_, big.data(), sizeof(int32_t) * big.size(), hipMemcpyHostToDevice));
-    d_rank_big_d0_ = Alloc<double>(n);
-    d_rank_big_d1_ = Alloc<double>(n);
-    d_rank_big_dh_ = Alloc<double>(n);
-    d_rank_big_f_ = Alloc<float>(n);
-    d_rank_big_i0_ = Alloc<int32_t>(n);
-    d_rank_big_i1_ = Alloc<int32_t>(n);
-    d_rank_big_i2_ = Alloc<int32_t>(n);
-    Log::Debug("device %s: %d queries of more than %d documents in global scratch",
-               kind == DeviceGradKind::Lambdarank ? "lambdarank" : "rank_xendcg", rank_num_big_, dev::kRankMaxDocs);
-  }
+  rank_tables_ = dev::UploadRankTables(r, kind, num_data_,
+                                       [this](size_t bytes) -> void* { return Alloc<char>(bytes); });
   uploaded_qb_src_ = r.query_boundaries;
 }
 

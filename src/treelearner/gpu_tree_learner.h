@@ -24,6 +24,7 @@
 #include <vector>
 
 #include "../device/kernels.h"
+#include "../device/rank_tables.h"
 #include "lgbm_amd/device_learner.h"
 #include "lgbm_amd/tuning.h"
 #include "serial_tree_learner.h"
@@ -407,21 +408,7 @@ class GPUTreeLearner : public SerialTreeLearner, public DeviceTreeLearner {
   const label_t* uploaded_weight_src_ = nullptr;
   const label_t* uploaded_lw_src_ = nullptr;
   // listwise objectives: query tables (uploaded once) and the xendcg generators
-  int32_t* d_qb_ = nullptr;
-  double* d_inv_max_dcg_ = nullptr;
-  double* d_label_gain_ = nullptr;
-  double* d_discount_ = nullptr;
-  double* d_sig_table_ = nullptr;  // lambdarank: the objective's sigmoid table
-  // listwise queries of more than kRankMaxDocs documents and their global scratch (RankArgs::big_*)
-  int32_t* d_rank_big_q_ = nullptr;
-  int32_t rank_num_big_ = 0;
-  double *d_rank_big_d0_ = nullptr, *d_rank_big_d1_ = nullptr, *d_rank_big_dh_ = nullptr;
-  int32_t rank_max_docs_ = 0;             // most documents of a query staged in LDS
-  float2* d_rank_pairs_ = nullptr;        // lambdarank pair scratch (RankArgs::pair_buf), or null
-  int64_t* d_rank_pair_off_ = nullptr;
-  float* d_rank_big_f_ = nullptr;
-  int32_t *d_rank_big_i0_ = nullptr, *d_rank_big_i1_ = nullptr, *d_rank_big_i2_ = nullptr;
-  uint32_t* d_rank_rng_ = nullptr;
+  dev::RankTables rank_tables_;
   const data_size_t* uploaded_qb_src_ = nullptr;
   // device row sampling (bagging / GOSS)
   uint32_t* d_sample_rng_ = nullptr;
@@ -444,16 +431,7 @@ class GPUTreeLearner : public SerialTreeLearner, public DeviceTreeLearner {
     void* metric_scratch = nullptr;
     data_size_t metric_scratch_rows = 0;  // rows metric_scratch is sized for (AUC)
     double* metric_out = nullptr;
-    struct QueryInputs {  // one query metric's device inputs (NDCG / MAP)
-      int32_t* qb = nullptr;
-      float* qw = nullptr;
-      int32_t* eval_at = nullptr;
-      double* qconst = nullptr;
-      double* label_gain = nullptr;
-      double* discount = nullptr;
-      void* scratch = nullptr;
-      bool big = false;  // a query longer than the LDS staging
-    };
+    using QueryInputs = dev::MetricQueryInputs;  // one query metric's device inputs (NDCG / MAP; AUC-mu: qconst)
     std::unordered_map<const void*, QueryInputs> queries;
     std::set<int> logged_kinds;  // metric kinds evaluated here so far (debug log)
   };

@@ -11,6 +11,7 @@ import numpy as np
 import pytest
 
 import lightgbmv1_amd as lgb
+from helpers.booster_probe import last_gradients as _last_gradients, train_scores as _train_scores
 
 pytestmark = pytest.mark.gpu
 
@@ -160,31 +161,6 @@ def test_listwise_gradients_on_device(gpu_available, objective):
         res[device] = _ndcg_at(y, b.predict(X), group)
     assert res["gpu"] > 0.7
     assert abs(res["gpu"] - res["cpu"]) < 0.02
-
-
-def _last_gradients(bst):
-    import ctypes
-    from lightgbmv1_amd.basic import _load_lib, _safe_call
-    _LIB = _load_lib()
-    n = ctypes.c_int64(0)
-    _safe_call(_LIB.LGBM_AMD_BoosterLastGradients(bst.handle, None, None, ctypes.byref(n)))
-    g = np.zeros(n.value, dtype=np.float32)
-    h = np.zeros(n.value, dtype=np.float32)
-    _safe_call(_LIB.LGBM_AMD_BoosterLastGradients(bst.handle, g.ctypes.data_as(ctypes.POINTER(ctypes.c_float)),
-                                                  h.ctypes.data_as(ctypes.POINTER(ctypes.c_float)), ctypes.byref(n)))
-    return g, h
-
-
-def _train_scores(bst, n):
-    """the booster's training scores (LGBM_BoosterGetPredict, data 0)"""
-    import ctypes
-    from lightgbmv1_amd.basic import _load_lib, _safe_call
-    buf = np.zeros(n, dtype=np.float64)
-    got = ctypes.c_int64(0)
-    _safe_call(_load_lib().LGBM_BoosterGetPredict(bst.handle, ctypes.c_int(0), ctypes.byref(got),
-                                                  buf.ctypes.data_as(ctypes.POINTER(ctypes.c_double))))
-    assert got.value == n
-    return buf
 
 
 @pytest.mark.parametrize("extra", [{}, {"lambdarank_norm": False}, {"weighted": True}, {"sigmoid": 2.5},

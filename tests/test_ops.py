@@ -35,7 +35,8 @@ def _t(a):
 def _ref_grad(obj, s, y, w, params):
     """float64 torch reference of the objective's (grad, hess)."""
     s, y = _t(s), _t(y)
-    w = _t(w) if w is not None else torch.ones_like(s)
+    weighted = w is not None
+    w = _t(w) if weighted else torch.ones_like(s)
     if obj == "regression":
         return (s - y) * w, w.clone()
     if obj == "regression_l1":
@@ -60,33 +61,86 @@ def _ref_grad(obj, s, y, w, params):
         e1, e2 = torch.exp((1 - r) * s), torch.exp((2 - r) * s)
         return (-y * e1 + e2) * w, (-y * (1 - r) * e1 + (2 - r) * e2) * w
     if obj == "binary":
+        # label weights (reference binary_objective.hpp:87-99): is_unbalance scales the rarer class
+        # up to the other's count, scale_pos_weight multiplies the positive class
         sig = params.get("sigmoid", 1.0)
-        lab = torch.where(y > 0, 1.0, -1.0).double()
+        pos = y > 0
+        npos, nneg = int(pos.sum()), int((~pos).sum())
+        lw = [1.0, 1.0]  # (negative, positive)
+        if params.get("is_unbalance"):
+            if npos > nneg:
+                lw[0] = npos / nneg
+            else:
+                lw[1] = nneg / npos
+        lw[1] *= params.get("scale_pos_weight", 1.0)
+        lab = torch.where(pos, 1.0, -1.0).double()
         resp = -lab * sig / (1 + torch.exp(lab * sig * s))
-        return resp * w, resp.abs() * (sig - resp.abs()) * w
+        ww = torch.where(pos, lw[1], lw[0]).double() * w
+        return resp * ww, resp.abs() * (sig - resp.abs()) * ww
     if obj == "cross_entropy":
         z = torch.sigmoid(s)
         return (z - y) * w, z * (1 - z) * w
+    if obj == "mape":
+        # label_weight = 1 / max(1, |y|) (* w), a float32 array; the hessian is w (reference
+        # regression_objective.hpp RegressionMAPELOSS)
+        lw = (1.0 / torch.clamp(y.abs(), min=1.0)).float() * w.float()
+        return torch.sign(s - y) * lw.double(), w.clone()
+    if obj == "regression_sqrt":
+        # reg_sqrt: trained on sign(y) * sqrt(|y|), kept as float32
+        ty = (torch.sign(y) * torch.sqrt(y.abs())).float().double()
+        return (s - ty) * w, w.clone()
+    if obj == "cross_entropy_lambda":
+        if not weighted:  # the unit-weight branch is cross entropy
+            z = torch.sigmoid(s)
+            return z - y, z * (1 - z)
+        # (reference xentropy_objective.hpp:196-211)
+        epf = torch.exp(s)
+        z = 1.0 - torch.exp(-w * torch.log(1.0 + epf))
+        g = (1.0 - y / z) * w / (1.0 + 1.0 / epf)
+        c = 1.0 / (1.0 - z)
+        a = w * epf / (1.0 + epf) ** 2
+        b = (c / (c - 1.0) ** 2) * (1.0 + w * epf - c)
+        return g, a * (1.0 + y * b)
     raise KeyError(obj)
 
 
+# (reference key of _ref_grad, data kind, parameters); the objective is params["objective"] where
+# it is not the key
 GRAD_CASES = [
     ("regression", "reg", {}), ("regression_l1", "reg", {}), ("huber", "reg", {"alpha": 0.7}),
     ("fair", "reg", {"fair_c": 1.3}), ("poisson", "pos", {"poisson_max_delta_step": 0.7}),
     ("quantile", "reg", {"alpha": 0.3}), ("gamma", "pos", {}), ("tweedie", "pos", {"tweedie_variance_power": 1.4}),
     ("binary", "bin", {"sigmoid": 1.7}), ("cross_entropy", "prob", {}),
+    # weighted and unweighted are the two branches of mape's label weights and of cross_entropy_lambda
+    ("mape", "reg", {}), ("cross_entropy_lambda", "prob", {}),
+    ("binary", "bin", {"scale_pos_weight": 3.0}), ("binary", "bin", {"is_unbalance": True}),
+    ("regression_sqrt", "reg", {"objective": "regression", "reg_sqrt": True}),
 ]
+GRAD_IDS = [c[0] + "".join("-" + k for k in c[2] if k in ("scale_pos_weight", "is_unbalance")) for c in GRAD_CASES]
 
 
-@pytest.mark.parametrize("obj,kind,params", GRAD_CASES, ids=[c[0] for c in GRAD_CASES])
+def _grad_data(obj, kind, weighted):
+    """_data with saturated scores among the binary / cross-entropy inputs: +-40, but +-8 for the
+    weighted cross_entropy_lambda, whose formula is not finite at +-40 in float64 (its z rounds to
+    0 and 1) in the reference either."""
+    s, y, w = _data(kind=kind)
+    if kind in ("bin", "prob"):
+        big = 8.0 if (obj == "cross_entropy_lambda" and weighted) else 40.0
+        s[:8] = np.array([1.0, -1.0, 1.0, -1.0, 0.9875, -0.9875, 1.0, -1.0]) * big
+        if kind == "bin":
+            y[:4] = [1.0, 1.0, 0.0, 0.0]  # (each class at each end)
+    return s, y, (w if weighted else None)
+
+
+@pytest.mark.parametrize("obj,kind,params", GRAD_CASES, ids=GRAD_IDS)
 @pytest.mark.parametrize("weighted", [False, True])
 def test_gradients_match_torch(obj, kind, params, weighted, gpu_available):
     from lightgbmv1_amd import ops
-    s, y, w = _data(kind=kind)
-    w = w if weighted else None
-    p = dict(params, objective=obj, verbose=-1)
+    s, y, w = _grad_data(obj, kind, weighted)
+    p = dict({"objective": obj}, verbose=-1, **params)
     g, h = ops.gradients(p, torch.tensor(s, device="cuda"), y, w)
     rg, rh = _ref_grad(obj, s, y, w, params)
+    assert torch.isfinite(rg).all() and torch.isfinite(rh).all()
     # the kernels compute in float64 and store float32 (score_t)
     np.testing.assert_allclose(g.cpu().double().numpy(), rg.float().double().numpy(), rtol=2e-6, atol=1e-6)
     np.testing.assert_allclose(h.cpu().double().numpy(), rh.float().double().numpy(), rtol=2e-6, atol=1e-6)
@@ -100,9 +154,8 @@ def test_gradients_and_bagging_with_poisoned_args(monkeypatch, gpu_available):
     monkeypatch.setenv("LGBM_AMD_POISON_ARGS", "1")
     for obj, kind, params in GRAD_CASES:
         for weighted in (False, True):
-            s, y, w = _data(kind=kind)
-            w = w if weighted else None
-            g, h = ops.gradients(dict(params, objective=obj, verbose=-1), torch.tensor(s, device="cuda"), y, w)
+            s, y, w = _grad_data(obj, kind, weighted)
+            g, h = ops.gradients(dict({"objective": obj}, verbose=-1, **params), torch.tensor(s, device="cuda"), y, w)
             rg, rh = _ref_grad(obj, s, y, w, params)
             np.testing.assert_allclose(g.cpu().double().numpy(), rg.float().double().numpy(), rtol=2e-6, atol=1e-6,
                                        err_msg=obj)
@@ -174,13 +227,15 @@ def test_metrics_match_torch(weighted, gpu_available):
 
 
 def _ref_bag(n, fraction, seed):
-    """the reference's bagging: generator Random(seed + b) per 1024-row block b."""
+    """the reference's bagging: generator Random(seed + b) per 1024-row block b; fraction may be
+    one value or one per row (balanced bagging)."""
     keep = np.zeros(n, dtype=bool)
+    fraction = np.broadcast_to(np.asarray(fraction, dtype=np.float64), (n,))
     for b in range((n + 1023) // 1024):
         x = (seed + b) & 0xFFFFFFFF
         for r in range(b * 1024, min(n, (b + 1) * 1024)):
             x = (214013 * x + 2531011) & 0xFFFFFFFF
-            keep[r] = ((x >> 16) & 0x7FFF) / 32768.0 < fraction
+            keep[r] = ((x >> 16) & 0x7FFF) / 32768.0 < fraction[r]
     return np.nonzero(keep)[0], np.nonzero(~keep)[0]
 
 
@@ -194,32 +249,59 @@ def test_bagging_matches_reference_generator(fraction, seed, gpu_available):
     np.testing.assert_array_equal(oob.cpu().numpy(), ro)
 
 
+def test_balanced_bagging_matches_reference_generator(gpu_available):
+    """Balanced bagging (reference gbdt.cpp BalancedBaggingHelper): the block's generator draws
+    once per row; rows of label > 0 are kept below pos_fraction, the others below neg_fraction."""
+    from lightgbmv1_amd import ops
+    n = 10 * 1024 + 77
+    label = (np.random.RandomState(2).rand(n) > 0.7).astype(np.float32)
+    bag, oob = ops.sample_rows(n, seed=3, label=label, pos_fraction=0.5, neg_fraction=0.8)
+    rb, ro = _ref_bag(n, np.where(label > 0, 0.5, 0.8), 3)
+    assert 0 < len(rb) < n
+    np.testing.assert_array_equal(bag.cpu().numpy(), rb)
+    np.testing.assert_array_equal(oob.cpu().numpy(), ro)
+
+
 def test_goss_keeps_top_rows_and_rescales(gpu_available):
-    """GOSS per 1024-row block: the top_rate largest |g*h| are kept as they are, other_rate
-    of the rest are sampled and multiplied by (cnt - top_k) / other_k."""
+    """GOSS per 1024-row block: the top_rate largest row weights -- the sum over the classes of
+    |g*h| in float32 (reference goss.hpp:107-112) -- are kept as they are, other_rate of the rest
+    are sampled and multiplied by (cnt - top_k) / other_k in every class."""
+    for num_class in (1, 3):
+        _check_goss(num_class)
+
+
+def _check_goss(num_class):
     from lightgbmv1_amd import ops
     n = 4 * 1024
     rng = np.random.RandomState(5)
-    g0 = rng.randn(n).astype(np.float32)
-    h0 = (rng.rand(n) + 0.1).astype(np.float32)
+    g0 = rng.randn(num_class, n).astype(np.float32)
+    h0 = (rng.rand(num_class, n) + 0.1).astype(np.float32)
+    if num_class == 1:
+        g0, h0 = g0[0], h0[0]
     g, h = torch.tensor(g0, device="cuda"), torch.tensor(h0, device="cuda")
     bag, _ = ops.sample_rows(n, goss=True, top_rate=0.2, other_rate=0.1, grad=g, hess=h, seed=9)
     bag = bag.cpu().numpy()
     gn, hn = g.cpu().numpy(), h.cpu().numpy()
     top_k, other_k = int(1024 * 0.2), int(1024 * 0.1)
     mult = np.float32(1024 - top_k) / other_k
+    wt_all = np.zeros(n, dtype=np.float32)
+    for k in range(num_class):  # (a float32 sum in class order, as the reference accumulates it)
+        wt_all += np.abs(g0[k] * h0[k]) if num_class > 1 else np.abs(g0 * h0)
     for b in range(4):
         rows = np.arange(b * 1024, (b + 1) * 1024)
-        wt = np.abs(g0[rows] * h0[rows])
+        wt = wt_all[rows]
         thr = np.sort(wt)[::-1][top_k - 1]
         top = rows[wt >= thr]
         inbag = bag[(bag >= rows[0]) & (bag <= rows[-1])]
         assert set(top) <= set(inbag)
         small = np.setdiff1d(inbag, top)
         assert len(small) == other_k
-        np.testing.assert_allclose(gn[small], g0[small] * mult, rtol=1e-6)
-        np.testing.assert_allclose(hn[small], h0[small] * mult, rtol=1e-6)
-        np.testing.assert_array_equal(gn[top], g0[top])
+        np.testing.assert_allclose(gn[..., small], g0[..., small] * mult, rtol=1e-6)
+        np.testing.assert_allclose(hn[..., small], h0[..., small] * mult, rtol=1e-6)
+        np.testing.assert_array_equal(gn[..., top], g0[..., top])
+        np.testing.assert_array_equal(hn[..., top], h0[..., top])
+        out = np.setdiff1d(rows, inbag)  # (rows left out keep their gradients too)
+        np.testing.assert_array_equal(gn[..., out], g0[..., out])
 
 
 def test_regression_family_metrics_match_torch(gpu_available):
