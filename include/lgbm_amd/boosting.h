@@ -121,6 +121,26 @@ class GBDT {
   // memory (raw scores, leaf indices or contributions); what is not applicable is an error
   void PredictDeviceBuffers(const void* d_data, bool is_double, int64_t nrow, int ncol, int start_iteration,
                             int num_iteration, DevicePredictKind kind, double* d_out, int64_t out_len);
+  // the same predictions of the rows of a host CSR matrix (indptr int32 / int64, nindptr = rows +
+  // 1 entries): each chunk of rows is scattered on the device into a compact matrix of the
+  // features the window's trees split on, which the same kernels walk.  Absent entries are 0,
+  // columns the model does not have are ignored, the last stored entry of a column wins.  false
+  // as for the dense matrix, or when not even one tile of rows fits the free memory
+  bool PredictCSROnDevice(const void* indptr, bool indptr_is_64, const int32_t* indices, const void* data,
+                          bool is_double, int64_t nindptr, int64_t nelem, int start_iteration, int num_iteration,
+                          DevicePredictKind kind, double* out);
+  // ... and of CSR arrays in device memory into out_len doubles of device memory; what is not
+  // applicable is an error
+  void PredictCSRDeviceBuffers(const void* d_indptr, bool indptr_is_64, const int32_t* d_indices, const void* d_data,
+                               bool is_double, int64_t nrow, int64_t nelem, int start_iteration, int num_iteration,
+                               DevicePredictKind kind, double* d_out, int64_t out_len);
+  // the compact matrix of host CSR rows evaluated on the host (tests; needs no device): the
+  // sorted features the window's trees split on into `used` (room for every feature, or null) and
+  // their count into *num_used; with `matrix` (row-major [rows][*num_used], of the data's type)
+  // the rows' values of those features
+  void CsrToSlotsOnHost(const void* indptr, bool indptr_is_64, const int32_t* indices, const void* data,
+                        bool is_double, int64_t nindptr, int64_t nelem, int start_iteration, int num_iteration,
+                        int32_t* num_used, int32_t* used, void* matrix);
   // predictions this process has computed on the device (tests: which path a call took)
   static int64_t DevicePredictions();
   // contributions of row-major float64 host rows from the path tables the device kernel reads,

@@ -256,6 +256,16 @@ LIGHTGBM_C_EXPORT int LGBM_AMD_BoosterDeviceCheckSplits(BoosterHandle handle, in
 LIGHTGBM_C_EXPORT int LGBM_AMD_BoosterPathTableContrib(BoosterHandle handle, const double* data, int32_t nrow,
                                                        int32_t ncol, int start_iteration, int num_iteration,
                                                        int64_t* out_len, double* out_result);
+// the compact matrix that device prediction of CSR rows builds, evaluated on the host with the
+// kernel's rule of a stored entry (no GPU needed): the sorted features that the trees of the
+// iteration window split on into out_used (room for every feature of the model, or null), their
+// count into *out_num_used, and with out_matrix (row-major [nindptr - 1][*out_num_used] of
+// data_type, or null) the rows' values of those features -- absent entries 0, columns the model
+// does not have ignored, the last stored entry of a column winning
+LIGHTGBM_C_EXPORT int LGBM_AMD_CsrToSlots(BoosterHandle handle, const void* indptr, int indptr_type,
+                                          const int32_t* indices, const void* data, int data_type, int64_t nindptr,
+                                          int64_t nelem, int start_iteration, int num_iteration,
+                                          int32_t* out_num_used, int32_t* out_used, void* out_matrix);
 // predictions this process has computed on the device, over all boosters (tests: whether a call
 // took the device path or the host predictor)
 LIGHTGBM_C_EXPORT int LGBM_AMD_DevicePredictCount(int64_t* out);

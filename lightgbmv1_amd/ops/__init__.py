@@ -183,13 +183,28 @@ def forest_predict(booster, X, kind="raw", start_iteration=0, num_iteration=-1):
     tensor ``[n, ncol]``, computed and left on the GPU as a float64 tensor: raw scores
     ``[n, classes]`` (``kind="raw"``), leaf indices ``[n, trees]`` (``"leaf"``) or SHAP
     contributions ``[n, classes * (num_features + 1)]`` (``"contrib"``).  Neither rows nor
-    results pass through the host, and any number of rows runs on the device."""
+    results pass through the host, and any number of rows runs on the device.
+
+    ``X`` may also be a ``torch.sparse_csr`` GPU tensor with float32 or float64 values (int32 or
+    int64 ``crow_indices``; int64 ``col_indices`` are converted to int32 on the device): absent
+    entries are 0, columns the model does not have are ignored, and the rows are scattered on
+    the device into a matrix of the features the trees split on (src/device/csr_kernels.hip)."""
     torch = _torch()
     if kind not in _FOREST_KINDS:
         raise LightGBMError("kind must be one of 'raw', 'leaf', 'contrib', got %r" % (kind,))
     if not isinstance(X, torch.Tensor) or X.dim() != 2 or X.dtype not in (torch.float32, torch.float64):
         raise LightGBMError("X must be a 2-d float32 or float64 torch tensor on the GPU")
-    data = _dev_ptr(X, X.dtype, "X")
+    sparse = X.layout == torch.sparse_csr
+    if sparse:
+        crow, col, values = X.crow_indices(), X.col_indices(), X.values()
+        if crow.dtype not in (torch.int32, torch.int64):
+            raise LightGBMError("crow_indices must be int32 or int64")
+        crow, values = crow.contiguous(), values.contiguous()
+        col = col.to(torch.int32).contiguous()
+        ptrs = (_dev_ptr(crow, crow.dtype, "crow_indices"), _dev_ptr(col, torch.int32, "col_indices"),
+                _dev_ptr(values, X.dtype, "values"))
+    else:
+        data = _dev_ptr(X, X.dtype, "X")
     n, ncol = X.shape
     start = max(0, int(start_iteration))
     num = int(num_iteration) if num_iteration is not None else -1
@@ -198,6 +213,13 @@ def forest_predict(booster, X, kind="raw", start_iteration=0, num_iteration=-1):
                  ctypes.c_int(start), ctypes.c_int(num), ctypes.byref(width))
     out = torch.empty((n, width.value), dtype=torch.float64, device=X.device)
     torch.cuda.synchronize(X.device)
+    if sparse:
+        _check(_lib().LGBMAMD_OpForestPredictCSR(
+            booster.handle, ptrs[0], ctypes.c_int(2 if crow.dtype == torch.int32 else 3), ptrs[1], ptrs[2],
+            ctypes.c_int(0 if X.dtype == torch.float32 else 1), ctypes.c_int64(n), ctypes.c_int64(values.numel()),
+            ctypes.c_int(_FOREST_KINDS[kind]), ctypes.c_int(start), ctypes.c_int(num),
+            _dev_ptr(out, torch.float64, "out"), ctypes.c_int64(out.numel())))
+        return out
     _check(_lib().LGBMAMD_OpForestPredict(booster.handle, data, ctypes.c_int(0 if X.dtype == torch.float32 else 1),
                                        ctypes.c_int64(n), ctypes.c_int32(ncol), ctypes.c_int(_FOREST_KINDS[kind]),
                                        ctypes.c_int(start), ctypes.c_int(num), _dev_ptr(out, torch.float64, "out"),

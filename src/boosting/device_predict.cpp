@@ -6,6 +6,11 @@
 // come from the same walk and SHAP contributions from the per-leaf path tables of shap_paths.h
 // (src/device/shap_kernels.hip).  Rows go through the device in chunks sized from the free
 // memory, so that a contribution matrix larger than HBM still predicts.
+//
+// CSR matrices (LGBM_BoosterPredictForCSR) take the same path: each chunk's rows are scattered on
+// the device into a compact matrix with one column per feature the window's trees split on
+// (FeatureSlots, src/device/csr_kernels.hip), and the forest is uploaded with its split features
+// rewritten to those columns, so the same kernels walk it.
 #include <hip/hip_runtime_api.h>
 #include <omp.h>
 
@@ -13,6 +18,7 @@
 #include <cstring>
 #include <vector>
 
+#include "../device/csr_slots.h"
 #include "../device/kernels.h"
 #include "shap_paths.h"
 #include "lgbm_amd/boosting.h"
@@ -58,8 +64,9 @@ struct DeviceBuffers {
 class DeviceForest {
  public:
   // false: the contribution kernel cannot run this forest (the host predicts)
+  // slots: the forest walks a compact matrix of the features it splits on (CSR rows)
   bool Upload(const std::vector<const Tree*>& trees, int num_class, int num_features, DevicePredictKind kind,
-              hipStream_t s) {
+              hipStream_t s, bool slots = false) {
     kind_ = kind;
     flat_.Build(trees);
     if (kind == DevicePredictKind::Contrib && (!paths_.Build(trees) || !paths_.FitsDevice())) return false;
@@ -67,7 +74,13 @@ class DeviceForest {
     f_.num_trees = static_cast<int32_t>(trees.size());
     f_.node_off = b_.Upload(flat_.node_off, s);
     f_.leaf_off = b_.Upload(flat_.leaf_off, s);
-    f_.feature = b_.Upload(flat_.feature, s);
+    if (slots) {
+      slots_.Build(flat_, num_features);
+      f_.feature = b_.Upload(slots_.feature, s);
+      slot_of_ = b_.Upload(slots_.slot_of, s);
+    } else {
+      f_.feature = b_.Upload(flat_.feature, s);
+    }
     f_.threshold = b_.Upload(flat_.threshold, s);
     f_.dtype = b_.Upload(flat_.dtype, s);
     f_.left = b_.Upload(flat_.left, s);
@@ -94,6 +107,8 @@ class DeviceForest {
     }
     return true;
   }
+  int NumSlots() const { return static_cast<int>(slots_.used.size()); }
+  const int32_t* SlotOf() const { return slot_of_; }
   // doubles of one row's output
   int64_t OutPerRow() const {
     if (kind_ == DevicePredictKind::Leaf) return f_.num_trees;
@@ -141,6 +156,8 @@ class DeviceForest {
   DevicePredictKind kind_ = DevicePredictKind::Raw;
   FlatForest flat_;
   ShapPathTables paths_;
+  FeatureSlots slots_;
+  const int32_t* slot_of_ = nullptr;
   DeviceBuffers b_;
   dev::ForestArgs f_{};
   dev::ShapArgs a_{};
@@ -254,6 +271,197 @@ void GBDT::PredictDeviceBuffers(const void* d_data, bool is_double, int64_t nrow
   if (nrow > 0) forest.Run(d_data, is_double, true, nrow, ncol, d_out, nullptr);
   HIPCHECK(hipStreamSynchronize(nullptr));
   ++g_device_predictions;
+}
+
+namespace {
+
+int64_t PtrAt(const void* indptr, bool is_64, int64_t i) {
+  return is_64 ? static_cast<const int64_t*>(indptr)[i] : static_cast<int64_t>(static_cast<const int32_t*>(indptr)[i]);
+}
+
+// the scatter of CSR rows [0, rows) (indptr on the device, entry_base = its first value) into d_mat
+void RunCsrToSlots(const DeviceForest& forest, const void* d_indptr, bool indptr_is_64, const int32_t* d_indices,
+                   const void* d_data, bool is_double, int64_t rows, int64_t entry_base, int64_t entries,
+                   int num_features, void* d_mat, hipStream_t s) {
+  dev::CsrSlotsArgs c{};
+  tuning::PoisonArgs(&c);  // (every field set below)
+  c.indptr_is_64 = indptr_is_64 ? 1 : 0;
+  c.is_double = is_double ? 1 : 0;
+  c.num_features = num_features;
+  c.num_slots = forest.NumSlots();
+  c.num_rows = rows;
+  c.entry_base = entry_base;
+  c.num_entries = entries;
+  c.indptr = d_indptr;
+  c.indices = d_indices;
+  c.data = d_data;
+  c.slot_of = forest.SlotOf();
+  c.out = d_mat;
+  dev::CsrToSlots(c, s);
+  HIPCHECK(hipGetLastError());
+}
+
+}  // namespace
+
+bool GBDT::PredictCSROnDevice(const void* indptr, bool indptr_is_64, const int32_t* indices, const void* data,
+                              bool is_double, int64_t nindptr, int64_t nelem, int start_iteration, int num_iteration,
+                              DevicePredictKind kind, double* out) {
+  int ndev = 0;
+  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return false;
+  const int64_t nrow = nindptr - 1;
+  if (num_tree_per_iteration_ > dev::kMaxPredClasses || nrow <= 0) return false;
+  // (rows are copied by their indptr entries: a matrix whose indptr does not ascend within the
+  // stored entries is left to the host)
+  if (PtrAt(indptr, indptr_is_64, 0) < 0 || PtrAt(indptr, indptr_is_64, nrow) > nelem) return false;
+  for (int64_t r = 0; r < nrow; ++r) {
+    if (PtrAt(indptr, indptr_is_64, r) > PtrAt(indptr, indptr_is_64, r + 1)) return false;
+  }
+  const int ntpi = num_tree_per_iteration_;
+  const int num_features = max_feature_idx_ + 1;
+  const std::vector<const Tree*> trees = PredictWindowTrees(start_iteration, num_iteration);
+  hipStream_t s;
+  HIPCHECK(hipStreamCreateWithFlags(&s, hipStreamNonBlocking));
+  bool ran = false;
+  {
+    DeviceForest forest;
+    if (forest.Upload(trees, ntpi, num_features, kind, s, true)) {
+      const size_t elem = is_double ? 8 : 4;
+      const size_t ptr_b = indptr_is_64 ? 8 : 4;
+      const int nslot = forest.NumSlots();
+      const int64_t per_out = forest.OutPerRow();
+      // rows per chunk: the compact matrix, the output, the accumulator tiles and the chunk's
+      // stored entries within most of the free memory
+      size_t free_b = 0, total_b = 0;
+      HIPCHECK(hipMemGetInfo(&free_b, &total_b));
+      const size_t per_row = static_cast<size_t>(nslot) * elem + static_cast<size_t>(per_out) * sizeof(double) + ptr_b;
+      const size_t per_entry = sizeof(int32_t) + elem;
+      const size_t budget = free_b - free_b / 5;
+      const size_t fixed = forest.ScratchBytes(nrow) + ptr_b;
+      int64_t chunk = budget > fixed ? static_cast<int64_t>((budget - fixed) / per_row) : 0;
+      chunk = std::max<int64_t>(dev::kShapLanes, chunk / dev::kShapLanes * dev::kShapLanes);
+      const int forced = tuning::Int(tuning::Knob::PredictChunkRows, 0);
+      if (forced > 0) chunk = forced;
+      chunk = std::min(chunk, nrow);
+      // the most stored entries of a chunk
+      auto most_entries = [&](int64_t rows) {
+        int64_t most = 0;
+        for (int64_t r0 = 0; r0 < nrow; r0 += rows) {
+          most = std::max(most, PtrAt(indptr, indptr_is_64, std::min(r0 + rows, nrow)) - PtrAt(indptr, indptr_is_64, r0));
+        }
+        return most;
+      };
+      int64_t entries = most_entries(chunk);
+      bool fits = true;
+      while (forced <= 0 && fixed + static_cast<size_t>(chunk) * per_row + static_cast<size_t>(entries) * per_entry > budget) {
+        if (chunk <= dev::kShapLanes) {
+          fits = false;
+          break;
+        }
+        chunk = std::max<int64_t>(dev::kShapLanes, chunk / 2 / dev::kShapLanes * dev::kShapLanes);
+        entries = most_entries(chunk);
+      }
+      if (fits) {
+        DeviceBuffers b;
+        void* d_indptr = b.Alloc(static_cast<size_t>(chunk + 1) * ptr_b);
+        int32_t* d_indices = static_cast<int32_t*>(b.Alloc(static_cast<size_t>(entries) * sizeof(int32_t)));
+        void* d_data = b.Alloc(static_cast<size_t>(entries) * elem);
+        void* d_mat = b.Alloc(static_cast<size_t>(chunk) * nslot * elem);
+        double* d_out = static_cast<double*>(b.Alloc(static_cast<size_t>(chunk) * per_out * sizeof(double)));
+        const bool convert = kind == DevicePredictKind::Normal;
+        std::vector<double> raw_out(convert ? static_cast<size_t>(nrow) * per_out : 0);
+        double* host_out = convert ? raw_out.data() : out;
+        for (int64_t r0 = 0; r0 < nrow; r0 += chunk) {
+          const int64_t rows = std::min(chunk, nrow - r0);
+          const int64_t e0 = PtrAt(indptr, indptr_is_64, r0);
+          const int64_t ne = PtrAt(indptr, indptr_is_64, r0 + rows) - e0;
+          HIPCHECK(hipMemcpyAsync(d_indptr, static_cast<const char*>(indptr) + static_cast<size_t>(r0) * ptr_b,
+                                  static_cast<size_t>(rows + 1) * ptr_b, hipMemcpyHostToDevice, s));
+          if (ne > 0) {
+            HIPCHECK(hipMemcpyAsync(d_indices, indices + e0, static_cast<size_t>(ne) * sizeof(int32_t),
+                                    hipMemcpyHostToDevice, s));
+            HIPCHECK(hipMemcpyAsync(d_data, static_cast<const char*>(data) + static_cast<size_t>(e0) * elem,
+                                    static_cast<size_t>(ne) * elem, hipMemcpyHostToDevice, s));
+          }
+          RunCsrToSlots(forest, d_indptr, indptr_is_64, d_indices, d_data, is_double, rows, e0, ne, num_features,
+                        d_mat, s);
+          forest.Run(d_mat, is_double, false, rows, nslot, d_out, s);
+          HIPCHECK(hipMemcpyAsync(host_out + r0 * per_out, d_out, static_cast<size_t>(rows) * per_out * sizeof(double),
+                                  hipMemcpyDeviceToHost, s));
+          HIPCHECK(hipStreamSynchronize(s));
+        }
+        ran = true;
+        ++g_device_predictions;
+        if (convert) {
+#pragma omp parallel for schedule(static)
+          for (int64_t r = 0; r < nrow; ++r) {
+            double* o = out + r * ntpi;
+            std::memcpy(o, raw_out.data() + r * ntpi, sizeof(double) * ntpi);
+            if (average_output_) {
+              for (int k = 0; k < ntpi; ++k) o[k] /= num_iteration_for_pred_;
+            }
+            if (objective_ != nullptr) objective_->ConvertOutput(o, o);
+          }
+        }
+      }
+    }
+  }
+  HIPCHECK(hipStreamDestroy(s));
+  return ran;
+}
+
+void GBDT::PredictCSRDeviceBuffers(const void* d_indptr, bool indptr_is_64, const int32_t* d_indices,
+                                   const void* d_data, bool is_double, int64_t nrow, int64_t nelem,
+                                   int start_iteration, int num_iteration, DevicePredictKind kind, double* d_out,
+                                   int64_t out_len) {
+  if (kind == DevicePredictKind::Normal) Log::Fatal("device buffers are predicted as raw scores, leaf indices or contributions");
+  if (num_tree_per_iteration_ > dev::kMaxPredClasses) {
+    Log::Fatal("forest prediction on the device handles at most %d trees per iteration", dev::kMaxPredClasses);
+  }
+  if (nrow < 0 || nelem < 0) Log::Fatal("CSR device buffers: %lld rows, %lld entries", static_cast<long long>(nrow), static_cast<long long>(nelem));
+  const std::vector<const Tree*> trees = PredictWindowTrees(start_iteration, num_iteration);
+  DeviceForest forest;
+  if (!forest.Upload(trees, num_tree_per_iteration_, max_feature_idx_ + 1, kind, nullptr, true)) {
+    Log::Fatal("contributions on the device need paths of at most %d distinct features and data counts on every node",
+               dev::kShapMaxPathLen - 1);
+  }
+  if (out_len != nrow * forest.OutPerRow()) {
+    Log::Fatal("output holds %lld doubles, the prediction has %lld", static_cast<long long>(out_len),
+               static_cast<long long>(nrow * forest.OutPerRow()));
+  }
+  if (nrow > 0) {
+    DeviceBuffers b;
+    void* d_mat = b.Alloc(static_cast<size_t>(nrow) * forest.NumSlots() * (is_double ? 8 : 4));
+    // (the rows are clamped to nelem entries in the kernel: indptr stays on the device)
+    RunCsrToSlots(forest, d_indptr, indptr_is_64, d_indices, d_data, is_double, nrow, 0, nelem, max_feature_idx_ + 1,
+                  d_mat, nullptr);
+    forest.Run(d_mat, is_double, false, nrow, forest.NumSlots(), d_out, nullptr);
+    HIPCHECK(hipStreamSynchronize(nullptr));
+  }
+  ++g_device_predictions;
+}
+
+void GBDT::CsrToSlotsOnHost(const void* indptr, bool indptr_is_64, const int32_t* indices, const void* data,
+                            bool is_double, int64_t nindptr, int64_t nelem, int start_iteration, int num_iteration,
+                            int32_t* num_used, int32_t* used, void* matrix) {
+  const std::vector<const Tree*> trees = PredictWindowTrees(start_iteration, num_iteration);
+  FlatForest flat;
+  flat.Build(trees);
+  FeatureSlots slots;
+  const int nf = max_feature_idx_ + 1;
+  slots.Build(flat, nf);
+  const int ns = static_cast<int>(slots.used.size());
+  *num_used = ns;
+  if (used != nullptr) std::copy(slots.used.begin(), slots.used.end(), used);
+  if (matrix == nullptr || nindptr <= 1) return;
+  const int64_t rows = nindptr - 1;
+  const int32_t* so = slots.slot_of.data();
+  if (is_double) {
+    if (indptr_is_64) dev::EvalCsrToSlots(static_cast<const int64_t*>(indptr), 0, indices, static_cast<const double*>(data), rows, nelem, so, nf, ns, static_cast<double*>(matrix));
+    else dev::EvalCsrToSlots(static_cast<const int32_t*>(indptr), 0, indices, static_cast<const double*>(data), rows, nelem, so, nf, ns, static_cast<double*>(matrix));
+  } else {
+    if (indptr_is_64) dev::EvalCsrToSlots(static_cast<const int64_t*>(indptr), 0, indices, static_cast<const float*>(data), rows, nelem, so, nf, ns, static_cast<float*>(matrix));
+    else dev::EvalCsrToSlots(static_cast<const int32_t*>(indptr), 0, indices, static_cast<const float*>(data), rows, nelem, so, nf, ns, static_cast<float*>(matrix));
+  }
 }
 
 int64_t GBDT::DevicePredictions() { return g_device_predictions.load(); }

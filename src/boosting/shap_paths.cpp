@@ -4,6 +4,7 @@
 #include <cstring>
 
 #include "../device/forest_decision.h"
+#include "lgbm_amd/log.h"
 
 namespace lgbm_amd {
 
@@ -48,6 +49,23 @@ void FlatForest::HostArgs(dev::ForestArgs* f) const {
   f->cat_bound = cat_bound.data();
   f->cat_bits_off = cat_bits_off.data();
   f->cat_bits = cat_bits.data();
+}
+
+void FeatureSlots::Build(const FlatForest& flat, int num_features) {
+  slot_of.assign(std::max(0, num_features), -1);
+  for (const int32_t f : flat.feature) {
+    if (f < 0 || f >= num_features) Log::Fatal("a tree splits on feature %d, the model has %d", f, num_features);
+    slot_of[f] = 0;
+  }
+  used.clear();
+  for (int f = 0; f < num_features; ++f) {
+    if (slot_of[f] == 0) {
+      slot_of[f] = static_cast<int32_t>(used.size());
+      used.push_back(f);
+    }
+  }
+  feature.resize(flat.feature.size());
+  for (size_t i = 0; i < feature.size(); ++i) feature[i] = slot_of[flat.feature[i]];
 }
 
 bool ShapPathTables::Build(const std::vector<const Tree*>& trees) {

@@ -29,6 +29,16 @@ struct FlatForest {
   void HostArgs(dev::ForestArgs* f) const;
 };
 
+// The distinct features a forest splits on, for sparse rows (src/device/csr_slots.h): used[] is
+// sorted, slot_of[feature] its position there (-1: no tree splits on the feature), and `feature`
+// is FlatForest::feature rewritten to slots, with which the forest kernels walk a compact
+// [rows x used.size()] matrix.  (ShapArgs::elem_feature keeps the real feature.)
+struct FeatureSlots {
+  std::vector<int32_t> used, slot_of, feature;
+
+  void Build(const FlatForest& flat, int num_features);
+};
+
 struct ShapPathTables {
   std::vector<int32_t> tree_leaf_off, leaf_elem_off, elem_feature, elem_pair_off, pairs;
   std::vector<double> leaf_value, elem_zero, expected, ratio;

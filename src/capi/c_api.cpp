@@ -427,13 +427,7 @@ class Booster {
                             int predict_type, int start_iteration, int num_iteration, const Config& cfg, double* out,
                             int64_t* out_len) {
     DevicePredictKind kind;
-    if (!DeviceKindOf(predict_type, &kind)) return false;
-    if (cfg.pred_early_stop || nrow < (kind == DevicePredictKind::Contrib ? kDeviceContribMinRows : 1024)) return false;
-    if (data_type != C_API_DTYPE_FLOAT32 && data_type != C_API_DTYPE_FLOAT64) return false;
-    if (cfg.device_type != "gpu" && config_.device_type != "gpu") return false;
-    const char* e = tuning::Get(tuning::Knob::HostPredict);
-    if (e != nullptr && e[0] == '1') return false;
-    if (!cfg.predict_disable_shape_check && ncol != boosting_->MaxFeatureIdx() + 1) return false;  // host path reports it
+    if (!DevicePredictGate(data_type, nrow, ncol, predict_type, cfg, &kind)) return false;
     std::unique_lock<std::shared_mutex> l(mu_);
     if (!boosting_->PredictDenseOnDevice(data, data_type == C_API_DTYPE_FLOAT64, nrow, ncol, is_row_major != 0,
                                          start_iteration, num_iteration, kind, out)) {
@@ -443,6 +437,72 @@ class Booster {
                boosting_->NumPredictOneRow(start_iteration, num_iteration, kind == DevicePredictKind::Leaf,
                                            kind == DevicePredictKind::Contrib);
     return true;
+  }
+
+  // whether a host matrix of nrow x ncol goes to the device (dense and CSR alike)
+  bool DevicePredictGate(int data_type, int64_t nrow, int64_t ncol, int predict_type, const Config& cfg,
+                         DevicePredictKind* kind) const {
+    if (!DeviceKindOf(predict_type, kind)) return false;
+    if (cfg.pred_early_stop || nrow < (*kind == DevicePredictKind::Contrib ? kDeviceContribMinRows : 1024)) return false;
+    if (data_type != C_API_DTYPE_FLOAT32 && data_type != C_API_DTYPE_FLOAT64) return false;
+    if (cfg.device_type != "gpu" && config_.device_type != "gpu") return false;
+    const char* e = tuning::Get(tuning::Knob::HostPredict);
+    if (e != nullptr && e[0] == '1') return false;
+    if (!cfg.predict_disable_shape_check && ncol != boosting_->MaxFeatureIdx() + 1) return false;  // host path reports it
+    return true;
+  }
+
+  // CSR rows under the same gate: each chunk of rows becomes a compact matrix of the features the
+  // trees split on (src/device/csr_kernels.hip) that the forest kernels walk.  Narrower and wider
+  // matrices (predict_disable_shape_check) need nothing more: missing features read 0 and
+  // columns the model does not have are ignored
+  bool PredictCSROnDevice(const void* indptr, int indptr_type, const int32_t* indices, const void* data,
+                          int data_type, int64_t nindptr, int64_t nelem, int64_t ncol, int predict_type,
+                          int start_iteration, int num_iteration, const Config& cfg, double* out, int64_t* out_len) {
+    DevicePredictKind kind;
+    if (indptr_type != C_API_DTYPE_INT32 && indptr_type != C_API_DTYPE_INT64) return false;
+    if (!DevicePredictGate(data_type, nindptr - 1, ncol, predict_type, cfg, &kind)) return false;
+    std::unique_lock<std::shared_mutex> l(mu_);
+    if (!boosting_->PredictCSROnDevice(indptr, indptr_type == C_API_DTYPE_INT64, indices, data,
+                                       data_type == C_API_DTYPE_FLOAT64, nindptr, nelem, start_iteration, num_iteration,
+                                       kind, out)) {
+      return false;
+    }
+    *out_len = (nindptr - 1) * boosting_->NumPredictOneRow(start_iteration, num_iteration,
+                                                           kind == DevicePredictKind::Leaf,
+                                                           kind == DevicePredictKind::Contrib);
+    return true;
+  }
+
+  // ... and CSR arrays in device memory, into device memory (ops.forest_predict on a sparse tensor)
+  void PredictCSRDeviceBuffers(const void* d_indptr, int indptr_type, const int32_t* d_indices, const void* d_data,
+                               int data_type, int64_t nrow, int64_t nelem, int predict_type, int start_iteration,
+                               int num_iteration, double* d_out, int64_t out_len) {
+    DevicePredictKind kind;
+    if (!DeviceKindOf(predict_type, &kind) || kind == DevicePredictKind::Normal) {
+      Log::Fatal("forest prediction on device buffers: predict type %d is not raw, leaf or contrib", predict_type);
+    }
+    if (data_type != C_API_DTYPE_FLOAT32 && data_type != C_API_DTYPE_FLOAT64) {
+      Log::Fatal("forest prediction on device buffers: data must be float32 or float64");
+    }
+    if (indptr_type != C_API_DTYPE_INT32 && indptr_type != C_API_DTYPE_INT64) {
+      Log::Fatal("forest prediction on device buffers: indptr must be int32 or int64");
+    }
+    std::unique_lock<std::shared_mutex> l(mu_);
+    boosting_->PredictCSRDeviceBuffers(d_indptr, indptr_type == C_API_DTYPE_INT64, d_indices, d_data,
+                                       data_type == C_API_DTYPE_FLOAT64, nrow, nelem, start_iteration, num_iteration,
+                                       kind, d_out, out_len);
+  }
+
+  void CsrToSlots(const void* indptr, int indptr_type, const int32_t* indices, const void* data, int data_type,
+                  int64_t nindptr, int64_t nelem, int start_iteration, int num_iteration, int32_t* num_used,
+                  int32_t* used, void* matrix) {
+    if (indptr_type != C_API_DTYPE_INT32 && indptr_type != C_API_DTYPE_INT64) Log::Fatal("Unknown indptr type");
+    if (data_type != C_API_DTYPE_FLOAT32 && data_type != C_API_DTYPE_FLOAT64) Log::Fatal("Unknown data type in CSR");
+    std::unique_lock<std::shared_mutex> l(mu_);
+    boosting_->CsrToSlotsOnHost(indptr, indptr_type == C_API_DTYPE_INT64, indices, data,
+                                data_type == C_API_DTYPE_FLOAT64, nindptr, nelem, start_iteration, num_iteration,
+                                num_used, used, matrix);
   }
 
   // raw scores, leaf indices or contributions of a row-major matrix in device memory, into
@@ -1102,9 +1162,13 @@ int LGBM_BoosterPredictForCSR(BoosterHandle handle, const void* indptr, int indp
   API_BEGIN();
   if (num_col <= 0) Log::Fatal("The number of columns should be greater than zero.");
   Config cfg = ParamsToConfig(parameter);
+  Booster* b = static_cast<Booster*>(handle);
+  if (b->PredictCSROnDevice(indptr, indptr_type, indices, data, data_type, nindptr, nelem, num_col, predict_type,
+                            start_iteration, num_iteration, cfg, out_result, out_len)) {
+    return 0;
+  }
   auto get = CSRRowFun(indptr, indptr_type, indices, data, data_type, nindptr, nelem);
-  static_cast<Booster*>(handle)->PredictRows(get, nindptr - 1, num_col, predict_type, start_iteration, num_iteration,
-                                              cfg, out_result, out_len);
+  b->PredictRows(get, nindptr - 1, num_col, predict_type, start_iteration, num_iteration, cfg, out_result, out_len);
   API_END();
 }
 
@@ -1119,12 +1183,23 @@ int LGBM_BoosterPredictSparseOutput(BoosterHandle handle, const void* indptr, in
   auto* b = static_cast<Booster*>(handle);
   std::vector<Row> rows;
   int64_t nrow, ncol;
+  const int ntpi = b->boosting()->NumModelPerIteration();
+  const int64_t width = ntpi * (b->boosting()->MaxFeatureIdx() + 2);
+  std::vector<double> dense;
+  int64_t dl = 0;
+  bool on_device = false;
   if (matrix_type == C_API_MATRIX_TYPE_CSR) {
-    auto get = CSRRowFun(indptr, indptr_type, indices, data, data_type, nindptr, nelem);
     nrow = nindptr - 1;
     ncol = num_col_or_row;
-    rows.resize(nrow);
-    for (int64_t i = 0; i < nrow; ++i) rows[i] = get(i);
+    // (the dense contributions from the device when the call is eligible, compressed below)
+    dense.resize(static_cast<size_t>(nrow) * width);
+    on_device = b->PredictCSROnDevice(indptr, indptr_type, indices, data, data_type, nindptr, nelem, ncol,
+                                      predict_type, start_iteration, num_iteration, cfg, dense.data(), &dl);
+    if (!on_device) {
+      auto get = CSRRowFun(indptr, indptr_type, indices, data, data_type, nindptr, nelem);
+      rows.resize(nrow);
+      for (int64_t i = 0; i < nrow; ++i) rows[i] = get(i);
+    }
   } else if (matrix_type == C_API_MATRIX_TYPE_CSC) {
     nrow = num_col_or_row;
     ncol = nindptr - 1;
@@ -1132,12 +1207,11 @@ int LGBM_BoosterPredictSparseOutput(BoosterHandle handle, const void* indptr, in
   } else {
     Log::Fatal("Unknown matrix type in LGBM_BoosterPredictSparseOutput");
   }
-  const int ntpi = b->boosting()->NumModelPerIteration();
-  const int64_t width = ntpi * (b->boosting()->MaxFeatureIdx() + 2);
-  std::vector<double> dense(static_cast<size_t>(nrow) * width);
-  int64_t dl = 0;
-  b->PredictRows([&rows](int64_t r) { return rows[r]; }, nrow, ncol, predict_type, start_iteration, num_iteration,
-                 cfg, dense.data(), &dl);
+  if (!on_device) {
+    dense.resize(static_cast<size_t>(nrow) * width);
+    b->PredictRows([&rows](int64_t r) { return rows[r]; }, nrow, ncol, predict_type, start_iteration, num_iteration,
+                   cfg, dense.data(), &dl);
+  }
   // per class k: matrix nrow x (nf+1).  CSR: indptr over (k, row); CSC: indptr over (k, col).
   const int64_t nfp1 = width / ntpi;
   std::vector<int64_t> ptr;
@@ -1525,6 +1599,15 @@ int LGBM_AMD_BoosterPathTableContrib(BoosterHandle handle, const double* data, i
   API_END();
 }
 
+int LGBM_AMD_CsrToSlots(BoosterHandle handle, const void* indptr, int indptr_type, const int32_t* indices,
+                        const void* data, int data_type, int64_t nindptr, int64_t nelem, int start_iteration,
+                        int num_iteration, int32_t* out_num_used, int32_t* out_used, void* out_matrix) {
+  API_BEGIN();
+  static_cast<Booster*>(handle)->CsrToSlots(indptr, indptr_type, indices, data, data_type, nindptr, nelem,
+                                            start_iteration, num_iteration, out_num_used, out_used, out_matrix);
+  API_END();
+}
+
 int LGBM_AMD_DevicePredictCount(int64_t* out) {
   API_BEGIN();
   *out = GBDT::DevicePredictions();
@@ -1538,6 +1621,15 @@ void BoosterPredictDeviceBuffers(BoosterHandle handle, const void* d_data, int d
                                  int64_t out_len) {
   static_cast<Booster*>(handle)->PredictDeviceBuffers(d_data, data_type, nrow, ncol, predict_type, start_iteration,
                                                       num_iteration, d_out, out_len);
+}
+// (LGBMAMD_OpForestPredictCSR)
+void BoosterPredictCSRDeviceBuffers(BoosterHandle handle, const void* d_indptr, int indptr_type,
+                                    const int32_t* d_indices, const void* d_data, int data_type, int64_t nrow,
+                                    int64_t nelem, int predict_type, int start_iteration, int num_iteration,
+                                    double* d_out, int64_t out_len) {
+  static_cast<Booster*>(handle)->PredictCSRDeviceBuffers(d_indptr, indptr_type, d_indices, d_data, data_type, nrow,
+                                                         nelem, predict_type, start_iteration, num_iteration, d_out,
+                                                         out_len);
 }
 }  // namespace lgbm_amd
 

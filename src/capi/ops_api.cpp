@@ -36,6 +36,10 @@ namespace lgbm_amd {
 void BoosterPredictDeviceBuffers(BoosterHandle handle, const void* d_data, int data_type, int64_t nrow, int32_t ncol,
                                  int predict_type, int start_iteration, int num_iteration, double* d_out,
                                  int64_t out_len);
+void BoosterPredictCSRDeviceBuffers(BoosterHandle handle, const void* d_indptr, int indptr_type,
+                                    const int32_t* d_indices, const void* d_data, int data_type, int64_t nrow,
+                                    int64_t nelem, int predict_type, int start_iteration, int num_iteration,
+                                    double* d_out, int64_t out_len);
 }  // namespace lgbm_amd
 
 namespace {
@@ -161,6 +165,20 @@ LIGHTGBM_C_EXPORT int LGBMAMD_OpForestPredict(BoosterHandle handle, const void* 
   return Guard([&] {
     BoosterPredictDeviceBuffers(handle, d_data, data_type, nrow, ncol, predict_type, start_iteration, num_iteration,
                                 d_out, out_len);
+  });
+}
+
+// the same predictions of nrow CSR rows in device memory (d_indptr: nrow + 1 int32 / int64
+// entries, indptr_type C_API_DTYPE_INT32 / INT64; d_indices: int32 columns; d_data: nelem float32
+// / float64 values): the rows are scattered into a compact matrix of the features the trees
+// split on (src/device/csr_kernels.hip), which the forest kernels walk.  Absent entries are 0
+LIGHTGBM_C_EXPORT int LGBMAMD_OpForestPredictCSR(BoosterHandle handle, const void* d_indptr, int indptr_type,
+                                                 const int32_t* d_indices, const void* d_data, int data_type,
+                                                 int64_t nrow, int64_t nelem, int predict_type, int start_iteration,
+                                                 int num_iteration, double* d_out, int64_t out_len) {
+  return Guard([&] {
+    BoosterPredictCSRDeviceBuffers(handle, d_indptr, indptr_type, d_indices, d_data, data_type, nrow, nelem,
+                                   predict_type, start_iteration, num_iteration, d_out, out_len);
   });
 }
 

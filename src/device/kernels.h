@@ -617,6 +617,27 @@ size_t ShapLdsBytes(const ShapArgs& a, bool phi_in_lds);
 int ShapTileGrid(int num_tiles);
 void ShapForest(const ForestArgs& f, const ShapArgs& a, hipStream_t s);
 
+// a chunk of CSR rows into the compact column-major matrix ([num_slots][num_rows]) that the
+// forest kernels read with a slot-rewritten ForestArgs::feature and row_major = 0
+// (src/device/csr_slots.h has the rule of an entry; src/device/csr_kernels.hip): zero-filled,
+// then every stored entry whose column has a slot, the last stored of a row's entries on one
+// column winning.  The matrix has the type of `data`
+struct CsrSlotsArgs {
+  int32_t indptr_is_64{};   // indptr: int64 (else int32)
+  int32_t is_double{};      // data and out: float64 (else float32)
+  int32_t num_features{};   // columns >= this are ignored
+  int32_t num_slots{};
+  int64_t num_rows{};
+  int64_t entry_base{};     // indptr[0]: indices / data start at the chunk's first entry
+  int64_t num_entries{};    // entries of indices / data (rows are clamped to them)
+  const void* indptr{};     // [num_rows + 1]
+  const int32_t* indices{};
+  const void* data{};
+  const int32_t* slot_of{};  // [num_features] slot of a feature, -1: no tree splits on it
+  void* out{};
+};
+void CsrToSlots(const CsrSlotsArgs& c, hipStream_t s);
+
 // validation metrics on device scores (one model per iteration)
 constexpr int kMetricL2 = 1, kMetricRMSE = 2, kMetricL1 = 3, kMetricBinLogloss = 4, kMetricBinError = 5,
               kMetricAUC = 6, kMetricQuantile = 7, kMetricHuber = 8, kMetricFair = 9, kMetricPoisson = 10,
