@@ -62,6 +62,11 @@ build_asan/lightgbm: $(ASAN_OBJS) $(DEV_OBJS) src/cli/main.cpp
 
 sanitize: build_asan/lightgbm
 
+# the growth rules alone (plain C++: no device objects, no HIP runtime) with their table driver
+build_asan/growth_plan_driver: src/treelearner/growth_plan.cpp tests/native/growth_plan_driver.cpp $(HEADERS)
+	@mkdir -p $(dir $@)
+	$(CXX) $(filter-out -O3 -fopenmp,$(CXXFLAGS)) $(ASAN_FLAGS) -o $@ tests/native/growth_plan_driver.cpp src/treelearner/growth_plan.cpp
+
 # ThreadSanitizer build of the host code: the C API driver
 # tests/native/tsan_driver.cpp linked from TSan-instrumented host objects (device objects
 # uninstrumented); OpenMP runs at one thread (libgomp is not instrumented)

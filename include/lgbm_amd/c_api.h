@@ -266,6 +266,12 @@ LIGHTGBM_C_EXPORT int LGBM_AMD_CsrToSlots(BoosterHandle handle, const void* indp
                                           const int32_t* indices, const void* data, int data_type, int64_t nindptr,
                                           int64_t nelem, int start_iteration, int num_iteration,
                                           int32_t* out_num_used, int32_t* out_used, void* out_matrix);
+// the device learner's growth rules evaluated on the host (no GPU, no dataset): how a learner
+// with these training parameters and these facts (a JSON object of GrowthFacts' fields,
+// src/treelearner/growth_plan.h; absent ones keep their defaults, environment knobs are facts
+// too and are not read) grows a tree -- the GrowthPlan as a JSON object
+LIGHTGBM_C_EXPORT int LGBM_AMD_GrowthPlan(const char* parameters, const char* facts_json, int64_t buffer_len,
+                                          int64_t* out_len, char* out_str);
 // predictions this process has computed on the device, over all boosters (tests: whether a call
 // took the device path or the host predictor)
 LIGHTGBM_C_EXPORT int LGBM_AMD_DevicePredictCount(int64_t* out);

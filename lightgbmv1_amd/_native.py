@@ -6,6 +6,7 @@ numpy <-> pointer conversion, parameter serialisation and the two-pass string-bu
 protocol of the ``Get...Names`` / ``SaveModelToString`` calls.
 """
 import ctypes
+import json
 
 import numpy as np
 
@@ -175,3 +176,10 @@ def read_names(fn, count):
 
 def string_array(strings):
     return (ctypes.c_char_p * len(strings))(*[s.encode("utf-8") for s in strings])
+
+
+def growth_plan(params, facts):
+    """The device learner's growth rules for training parameters `params` and the learner's
+    `facts` (dicts), evaluated on the host by LGBM_AMD_GrowthPlan: the plan as a dict."""
+    return json.loads(read_string(lambda size, need, buf: call(
+        "LGBM_AMD_GrowthPlan", cstr(params_str(params)), cstr(json.dumps(facts)), size, need, buf), 1 << 12))

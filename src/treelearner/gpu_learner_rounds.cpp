@@ -65,36 +65,19 @@ void GPUTreeLearner::AllocRoundState() {
   a.cbest_cat = d_cbest_cat_;
   a.child_cnt = d_child_cnt_;
   round_hist_.clear();
-  // per-node sampling on round growth (KArgs::round_bynode): one process or the data- /
-  // feature-parallel learners (every rank draws the same samples; k_round_childbest completes
-  // each rank's per-node results and flags from the gathered records), no interaction
-  // constraints (categorical features: their category sets are kept per node)
-  bool any_cat = false;
-  for (int f = 0; f < num_features_; ++f) any_cat = any_cat || data_->FeatureBinMapper(f)->bin_type() == BinType::Categorical;
-  const bool base_rounds = config_->interaction_constraints_vector.empty() && !voting_;
-  const bool simple_rounds = base_rounds && !any_cat;
+  // the order-dependent modes round growth replays (KArgs::round_bynode / round_xt /
+  // round_cegb): decided now, with the buffers they need (k_round_childbest completes each
+  // rank's per-node results and flags from the gathered records)
+  GrowthFacts facts = Facts();
+  facts.round_allocated = false;
+  const GrowthPlan plan = PlanGrowth(*config_, facts);
+  const bool bynode = plan.round_bynode, xt = plan.round_xt, cegb = plan.round_cegb;
   // (categorical features: each node keeps its categorical features' category sets)
   std::vector<int32_t> cat_slot(std::max(1, num_features_), -1);
   int ncs = 0;
   for (int f = 0; f < num_features_; ++f) {
     if (data_->FeatureBinMapper(f)->bin_type() == BinType::Categorical) cat_slot[f] = ncs++;
   }
-  const double cat_bytes = static_cast<double>(split_rows_) * ncs * kMaxCatWords * sizeof(uint32_t);
-  const bool bynode = config_->feature_fraction_bynode < 1.0 && base_rounds && cat_bytes <= 2.0 * (1ull << 30) &&
-                      !tuning::Off(tuning::Knob::ByNodeRounds);
-  // extra_trees on round growth (KArgs::round_xt): also no CEGB or forced splits, at most
-  // kXtLaneFeatures * 64 features (the replay's draw counters), prefix tables under 8 GiB
-  const double pre_bytes = static_cast<double>(split_rows_) * total_bins_ * sizeof(dev::XtPre);
-  const bool xt = config_->extra_trees && simple_rounds && !distributed_ && !CostEffectiveGB::Enabled(*config_) &&
-                  config_->forcedsplits_filename.empty() && num_features_ <= 4 * 64 &&
-                  pre_bytes <= 8.0 * (1ull << 30) && !tuning::Off(tuning::Knob::XtRounds);
-  // CEGB coupled penalties on round growth (KArgs::round_cegb): also no lazy penalties or
-  // monotone constraints (the replay subtracts the penalties from raw candidates)
-  const bool mono = std::any_of(config_->monotone_constraints.begin(), config_->monotone_constraints.end(),
-                                [](int8_t m) { return m != 0; });
-  const bool cegb = CostEffectiveGB::Enabled(*config_) && !config_->cegb_penalty_feature_coupled.empty() &&
-                    config_->cegb_penalty_feature_lazy.empty() && simple_rounds && !mono &&
-                    !tuning::Off(tuning::Knob::CegbRounds);
   const size_t nf = static_cast<size_t>(std::max(1, num_features_));
   if (bynode || xt || cegb) {
     a.leaf_rows = Alloc<int8_t>(static_cast<size_t>(config_->num_leaves) * nf);
@@ -225,18 +208,12 @@ void GPUTreeLearner::AutoGrowthRecord(double ms) {
   ++auto_tree_;
 }
 
-bool GPUTreeLearner::RoundGrowth(const dev::KArgs& a) const {
-  if (round_k_ <= 1 || d_round_ == nullptr) return false;
-  if (distributed_ && Network::device_comm() == nullptr) return false;  // (host collectives: one split per step)
-  // the split order depends on more than each leaf's own rows: per-node feature samples and
-  // extra_trees draws are consumed in the sequential order, CEGB's coupled penalties change
-  // other leaves' gains, forced splits follow their own schedule
-  // (per-node sampling without interaction constraints folds each node's sample at the replay:
-  // KArgs::round_bynode)
-  if (a.node_mask != nullptr && !(a.round_bynode && a.bynode_rng == nullptr)) return false;
-  if ((a.xt_base != nullptr && !a.round_xt) || a.forced_n > 0 || a.p.mono_inter) return false;
-  if (a.p.cegb && !CegbRounds(a)) return false;
-  return true;
+// whether this tree may grow in rounds: the plan's answer (PlanGrowth: per-node feature samples
+// and extra_trees draws are consumed in the sequential order, CEGB's coupled penalties change
+// other leaves' gains, forced splits follow their own schedule)
+bool GPUTreeLearner::RoundGrowth() const {
+  if (plan_.growth == Growth::kRoundsOnceSampleUsed) return CegbRounds();
+  return plan_.growth == Growth::kRounds;
 }
 
 // CEGB on round growth (one process or data- / feature-parallel, no lazy penalties).  A scan subtracts the split penalty,
@@ -247,10 +224,10 @@ bool GPUTreeLearner::RoundGrowth(const dev::KArgs& a) const {
 // tree grows in rounds once every feature of its sample is used -- its splits cannot use a new
 // feature, the coupled terms are 0 and no refund happens; the candidates a refund would read
 // later are of features outside this tree's sample (not scanned here).  Earlier trees grow one
-// split per step, as do all trees with lazy penalties.
-bool GPUTreeLearner::CegbRounds(const dev::KArgs& a) const {
-  if (voting_ || a.cegb_lazy != nullptr || cegb_ == nullptr) return false;
-  if (a.cegb_coupled == nullptr || a.round_cegb) return true;  // (round_cegb: refunds in the replay)
+// split per step, as do all trees with lazy penalties.  (With KArgs::round_cegb the replay
+// refunds, and every tree grows in rounds.)
+bool GPUTreeLearner::CegbRounds() const {
+  if (cegb_ == nullptr) return false;
   const std::vector<char>& used = cegb_->used_in_split();
   for (int f = 0; f < num_features_; ++f) {
     if (h_mask_[f] && (f >= static_cast<int>(used.size()) || !used[f])) return false;

@@ -1,10 +1,15 @@
 // MI355X tree learner host orchestration (see gpu_tree_learner.h).
 #include "gpu_learner_internal.h"
+#include "growth_limits.h"
 #include "lgbm_amd/tuning.h"
 
 namespace lgbm_amd {
 
 namespace {
+
+// bins of a histogram column tile (the split kernel's LDS holds the tile histogram, 8 or 16
+// bytes per bin): 8Ki, or 16Ki for packed histograms when no narrower tile fits
+constexpr int kTileBins = 8 << 10, kTileBinsPackedMax = 16 << 10;
 
 int PickDevice(const Config* cfg) {
   int count = 0;
@@ -307,7 +312,7 @@ void GPUTreeLearner::UploadData() {
   int max_tw = 1 << 20;
   if (const char* e = tuning::Get(tuning::Knob::HistTileWords)) max_tw = std::max(1, std::atoi(e));
   int tile_words = sparse_rows_ ? 1 : 0;  // (row-sparse tiles are bin ranges, below)
-  const std::vector<int> limits = hist_units_ == 1 ? std::vector<int>{8192, 16384} : std::vector<int>{8192};
+  const std::vector<int> limits = hist_units_ == 1 ? std::vector<int>{kTileBins, kTileBinsPackedMax} : std::vector<int>{kTileBins};
   for (int limit : limits) {
     if (sparse_rows_) break;
     for (int tw = std::min({wpr, dev::kHistThreads, max_tw}); tw >= 1; --tw) {
@@ -320,39 +325,20 @@ void GPUTreeLearner::UploadData() {
   }
   if (tile_words == 0) Log::Fatal("device learner: feature groups too wide for LDS histograms; reduce max_bin");
   num_cat_total_ = 0;
-  for (const auto& F : feats) num_cat_total_ += F.is_cat ? 1 : 0;
+  max_cat_bins_ = 0;
+  for (const auto& F : feats) {
+    num_cat_total_ += F.is_cat ? 1 : 0;
+    if (F.is_cat) max_cat_bins_ = std::max(max_cat_bins_, F.num_bin);
+  }
   args_.tile_words = tile_words;
   SetupOwnership();
   const int n_leaves = config_->num_leaves;
-  // round growth: up to round_k_ leaves expanded per round (LGBM_AMD_ROUND_K, 1 = one split per
-  // step; distributed learners run rounds with a device communicator)
-  // Without LGBM_AMD_ROUND_K the width adapts per tree (RunRounds): 8 while the last tree's
-  // speculation was accepted (expansions <= splits + 2: early trees), else 6 (A/B at 300
-  // iterations of the headline, profiles/r04_round_width.md: K=8 saves 2 rounds on the first
-  // trees for 2 more expansions, later it adds 8-10 unaccepted ones; fixed K 6 / 8 / 10 =
-  // 2.040 / 2.072 / 2.132 ms, window of 20 after 5: 2.148 / 2.075)
-  // Below 4M rows per rank the width stays 8: a round there is latency-bound and the extra
-  // speculation is nearly free (r04_round_width.md: 1.25M / 2.5M rows 0.929 / 1.106 ms fixed
-  // vs 0.943 / 1.120 adaptive; Epsilon 8.28 vs 8.44 ms, Bosch / LTR shapes equal)
-  // (the rows per rank are averaged over the ranks at the first tree, RunRounds: every rank
-  // must plan with the same width)
-  // Trees of 90 leaves or more run num_leaves / 10 expansions per round (at most 16), fixed:
-  // at 255 leaves width 16 halves the rounds per tree (41 -> 23) and saves 11-22% per
-  // iteration on every 255-leaf shape measured (config #2 at 255 / 63 / 15 bins, the five
-  // config #3 workloads; the same trees); at 127 leaves width 12 beats 8 and 16 (2.73 vs 2.88
-  // / 2.80 ms: profiles/r06_round_width_255.md)
-  round_k_ = tuning::kRoundWidth;
-  k_adapt_ = true;
+  // round growth: up to round_k_ leaves expanded per round (the plan's initial width)
+  round_k_ = 0;  // (not fixed yet)
+  const GrowthPlan width = PlanGrowth(*config_, Facts());
+  round_k_ = width.round_width;
+  k_adapt_ = width.width_adapts;
   k_adapt_checked_ = false;
-  if (n_leaves / tuning::kRoundLeavesPerWidth > tuning::kRoundWidth) {
-    round_k_ = n_leaves / tuning::kRoundLeavesPerWidth;
-    k_adapt_ = false;
-  }
-  if (const char* e = tuning::Get(tuning::Knob::RoundK)) {
-    round_k_ = std::atoi(e);
-    k_adapt_ = false;
-  }
-  round_k_ = std::max(1, std::min(dev::kMaxRoundExp, round_k_));
   // speculation below the leaves (LGBM_AMD_ROUND_VMAX levels, 0: leaves only): one index
   // buffer per level + 2 (device_types.h), bounded to 32 GiB of row indices
   round_vmax_ = dev::kMaxRoundVmax;
@@ -405,8 +391,8 @@ void GPUTreeLearner::UploadData() {
   // CU in all, since the smaller leaves' blocks exit at once and their launches alone cost
   // tens of microseconds (Epsilon, 8 column tiles: 37.4 ms/iter at 256 x 8, 28.7 at 32 x 8;
   // Yahoo, 3 tiles: 20.8 at 256 x 3, 20.6 at 64 x 3 -- profiles/r02_v10_split_grid_wide.txt)
-  // column tiles of the histogram kernels (row-sparse: bin ranges of 16384 packed / 8192 wide bins)
-  const int sparse_tile_bins = hist_units_ == 1 ? 16384 : 8192;
+  // column tiles of the histogram kernels (row-sparse: bin ranges of kTileBinsPackedMax packed / kTileBins wide bins)
+  const int sparse_tile_bins = hist_units_ == 1 ? kTileBinsPackedMax : kTileBins;
   const int col_tiles = sparse_rows_ ? (total_bins_ + sparse_tile_bins - 1) / sparse_tile_bins
                                      : (wpr + tile_words - 1) / tile_words;
   split_grid_ = std::max(std::min(8, dev::HistGridBlocks() / 2), dev::HistGridBlocks() / 2 / std::max(1, col_tiles));
@@ -552,7 +538,7 @@ void GPUTreeLearner::UploadData() {
   a.sp_ptr = d_sp_ptr_;
   a.sp_bin = d_sp_bin_;
   a.sp_team = sp_team_;
-  if (sparse_rows_) {  // column tiles = bin ranges of at most 16384 (packed) / 8192 (wide) bins
+  if (sparse_rows_) {  // column tiles = bin ranges of at most kTileBinsPackedMax (packed) / kTileBins (wide) bins
     a.tile_bins = (total_bins_ + a.hist_tiles - 1) / a.hist_tiles;
     a.tile_w0 = 0;
     a.tile_w1 = a.hist_tiles;
@@ -688,12 +674,12 @@ void GPUTreeLearner::UploadData() {
   AllocSplittable();
 }
 
-// interaction constraints as per-feature constraint bitmasks (device-resident growth
-// supports up to dev::kMaxIcConstraints = 256 constraints, see DecideMode); rebuilt when the config changes
+// interaction constraints as per-feature constraint bitmasks (more constraints than the masks
+// hold grow host-assisted, PlanGrowth); rebuilt when the config changes
 void GPUTreeLearner::UploadInteractionMasks() {
   const auto& ic = config_->interaction_constraints_vector;
   args_.feat_icmask = nullptr;
-  if (ic.empty() || ic.size() > static_cast<size_t>(dev::kMaxIcConstraints)) return;
+  if (ic.empty() || ic.size() > static_cast<size_t>(DeviceGrowthLimits().max_ic_constraints)) return;
   std::vector<dev::IcMask> icm(std::max(1, num_features_), dev::IcMask{});
   for (int f = 0; f < num_features_; ++f) {
     const int real = data_->RealFeatureIndex(f);
@@ -793,74 +779,57 @@ void GPUTreeLearner::ResetConfig(const Config* config) {
   h_feats_ = feats;
 }
 
+GrowthFacts GPUTreeLearner::Facts() const {
+  GrowthFacts f;
+  f.limits = DeviceGrowthLimits();
+  FillKnobFacts(&f);
+  f.kind = mode_;
+  f.world = world_;
+  f.force_host = f.force_host || force_host_mode_;
+  f.device_comm = Network::device_comm() != nullptr;
+  f.num_features = num_features_;
+  f.num_categorical = num_cat_total_;
+  f.max_cat_bins = max_cat_bins_;
+  f.total_bins = total_bins_;
+  f.forced = forced_state_;
+  f.round_k = round_k_;
+  f.split_rows = split_rows_;
+  f.round_allocated = round_k_ > 1 && d_round_ != nullptr;
+  f.alloc_bynode = args_.round_bynode != 0;
+  f.alloc_xt = args_.round_xt != 0;
+  f.alloc_cegb = args_.round_cegb != 0;
+  f.spec_allowed = spec_allowed_;
+  f.bagging = use_bag_;
+  f.host_out = tree_out_used_;
+  f.ktrace = args_.ktrace != nullptr;
+  f.num_tree_per_iteration = num_tree_per_iteration_;
+  f.timed_rounds = auto_state_ == kAutoRounds;
+  return f;
+}
+
 void GPUTreeLearner::DecideMode() {
-  bool dm = true;
-  const char* force = tuning::Get(tuning::Knob::HostAssist);
-  if ((force != nullptr && force[0] == '1') || force_host_mode_) dm = false;
-  bool any_cat = false;
-  for (int f = 0; f < num_features_ && dm; ++f) {
-    // categorical splits are scanned on the device up to kFindMaxCatBins categories
-    const BinMapper* m = data_->FeatureBinMapper(f);
-    if (m->bin_type() == BinType::Categorical) any_cat = true;
-    if (m->bin_type() == BinType::Categorical && m->num_bin() > dev::kFindMaxCatBins) dm = false;
+  // the device schedule of the forced splits (KArgs::forced_*): not built for a distributed
+  // learner that cannot gather the forced records; without forced splits a stale one is cleared
+  forced_state_ = ForcedSplits::kNone;
+  if (has_forced_split_) {
+    const bool built = !(distributed_ && !ForcedGathered()) && SetupForcedSplits();
+    forced_state_ = built ? ForcedSplits::kScheduled : ForcedSplits::kRefused;
+  } else if (args_.forced_n > 0) {
+    SetupForcedSplits();
   }
-  // extra_trees: random thresholds are drawn on the device (categorical ones by the workgroup
-  // that scans both children of the feature in order); the distributed learners keep
-  // categorical draws host-assisted
-  if (config_->extra_trees && any_cat && distributed_) dm = false;
-  // interaction constraints: on the device up to 256 constraints; with per-node sampling the
-  // children's masks are drawn on the device after each partition (k_bynode_step) -- under the
-  // distributed learners too: every rank picks the same split, so every rank's generator draws
-  // the same masks
-  const auto& ic = config_->interaction_constraints_vector;
-  if (!ic.empty() && ic.size() > static_cast<size_t>(dev::kMaxIcConstraints)) dm = false;
-  // intermediate monotone constraints re-bound leaves all over the tree after a split: the pick
-  // walks the tree and the next split scan re-scans the re-bounded leaves (one process, one
-  // split per step; with extra_trees draws, forced splits or more than kMonoInterMaxLeaves
-  // leaves the host loop does it between the device histogram builds)
-  const bool mono_inter = config_->monotone_constraints_method == "intermediate" &&
-                          std::any_of(config_->monotone_constraints.begin(), config_->monotone_constraints.end(),
-                                      [](int8_t m) { return m != 0; });
-  if (mono_inter && (distributed_ || config_->extra_trees || has_forced_split_ ||
-                     config_->num_leaves > dev::kMonoInterMaxLeaves)) {
-    dm = false;
-  }
-  // voting: extra_trees draws stay with the host voting loop -- its local scans skip the
-  // features their parent's local scan could not split and draw from the feature generators,
-  // its global scans draw from a second generator set on the rank that owns each elected
-  // histogram (reference feature_metas_); per-node sampling runs on the device (the global
-  // scan's masks)
-  if (voting_ && config_->extra_trees && any_cat) dm = false;
-  // CEGB: split and coupled feature penalties are applied by the device scans (single rank);
-  // lazy penalties (per-row usage bitsets) and distributed CEGB run host-assisted
-  const bool cegb = CostEffectiveGB::Enabled(*config_);
-  // forced splits: applied by the pick (the static BFS schedule of the JSON tree); under the
-  // feature-parallel learner the owner of a forced node's feature computes its record and every
-  // rank picks it from the gathered records (the data-parallel learner rejects forced splits, as
-  // the reference does; voting keeps them host-assisted).  Per-node sampling and CEGB split / coupled penalties run
-  // device-resident under the distributed learners too: every rank draws the same node samples
-  // and holds the same CEGB state, the owners' scans apply them (LGBM_AMD_DIST_HOST_ASSIST=1:
-  // the host-assisted fallback, for A/B)
-  const char* dha = tuning::Get(tuning::Knob::DistHostAssist);
-  const bool dist_fallback = distributed_ && dha != nullptr && dha[0] == '1';
-  if (has_forced_split_ && ((distributed_ && !ForcedGathered()) || !SetupForcedSplits())) dm = false;
-  if (!has_forced_split_ && args_.forced_n > 0) SetupForcedSplits();  // (cleared)
-  if ((config_->feature_fraction_bynode < 1.0 && dist_fallback) ||
-      (cegb && ((!config_->cegb_penalty_feature_lazy.empty() && (distributed_ || num_features_ > 8192)) ||
-                dist_fallback))) {
-    dm = false;
-  }
-  if (cegb && dm && !args_.p.cegb) SetupCegb();
-  if (mono_inter && dm && !args_.p.mono_inter) SetupMonoInter();
-  if (!(mono_inter && dm) && args_.p.mono_inter) {
+  plan_ = PlanGrowth(*config_, Facts());
+  if (plan_.cegb && !args_.p.cegb) SetupCegb();
+  if (plan_.mono_inter && !args_.p.mono_inter) SetupMonoInter();
+  if (!plan_.mono_inter && args_.p.mono_inter) {
     args_.p.mono_inter = 0;
     DestroyGraph();
   }
-  if (dm != device_mode_ || !mode_decided_) {
+  if (plan_.device_resident != device_mode_ || !mode_decided_) {
     mode_decided_ = true;
-    Log::Debug("device learner: %s growth", dm ? "device-resident" : "host-assisted");
+    if (plan_.device_resident) Log::Debug("device learner: device-resident growth");
+    else Log::Debug("device learner: host-assisted growth (%s)", plan_.reason);
   }
-  device_mode_ = dm;
+  device_mode_ = plan_.device_resident;
 }
 
 void GPUTreeLearner::SetBaggingData(const Dataset* subset, const data_size_t* used_indices, data_size_t n) {
@@ -1209,6 +1178,58 @@ Tree* GPUTreeLearner::TrainDeviceMode(bool speculated) {
     for (int f = 0; f < num_features_; ++f) h_mask_[f] = mask[f];
   }
   OwnershipForTree();
+  const dev::KArgs a = PrepareTreeArgs();
+  last_stats_.rounds = 0;
+  last_stats_.expansions = 0;
+  last_stats_.graph = false;
+  last_stats_.speculated = speculated;
+  const bool can_round = RoundGrowth();
+  const bool rounds = can_round && AutoGrowthRounds();
+  const auto t_grow = std::chrono::steady_clock::now();
+  const int num_splits = GrowTree(a, rounds, speculated);
+  if (can_round) {
+    AutoGrowthRecord(std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_grow).count());
+  }
+  last_stats_.device_mode = true;
+  last_stats_.splits = num_splits;
+  // every step's collectives run (exiting early once the tree is done): the sequence is fixed
+  if (!rounds) {
+    last_stats_.collective_bytes =
+        distributed_ ? root_collective_bytes_ + split_collective_bytes_ * (config_->num_leaves - 1) : 0.0;
+  }
+  ReplayHostGenerators(a, rounds, num_splits);
+  if (a.ktrace != nullptr && !rounds) ReportKernelTrace(num_splits);
+  if (const char* kp = tuning::Get(tuning::Knob::KernelProbe)) {
+    if (kp[0] == '1' && !rounds) KernelFloorProbe(a);
+  }
+  // the promised training-score update (ExpectTrainingScoreUpdate), on the device before the
+  // host builds the tree
+  // round growth: the tree's last plan wrote the split records to the host (KArgs::host_out),
+  // or they are copied now (one record per split) and the host waits for that copy only
+  const double shrink = train_shrink_;
+  const dev::SplitRecord* recs = h_rec_;
+  const bool copy_recs = rounds && num_splits > 0 && !tree_out_used_;
+  if (rounds && tree_out_used_) recs = reinterpret_cast<const dev::SplitRecord*>(h_tree_out_ + dev::kHostOutHeaderWords);
+  if (copy_recs) {
+    HIPCHECK(hipMemcpyAsync(h_rec_, d_rec_, sizeof(dev::SplitRecord) * num_splits, hipMemcpyDeviceToHost, stream_));
+    if (rec_event_ == nullptr) HIPCHECK(hipEventCreateWithFlags(&rec_event_, hipEventDisableTiming));
+    HIPCHECK(hipEventRecord(rec_event_, stream_));
+  }
+  if (shrink != 0.0 && num_splits >= 1 && FusedScoreWalk(num_splits + 1, 0) && !tuning::Off(tuning::Knob::EarlyScore)) {
+    EarlyScoreUpdate(num_splits, shrink);
+  }
+  if (copy_recs) HIPCHECK(hipEventSynchronize(rec_event_));
+  std::unique_ptr<Tree> tree(TreeFromRecords(recs, num_splits));
+  // the records are consumed: the next tree may be launched now (its last plan rewrites them)
+  const bool spec_ok = rounds && SpeculationEligible() && early_scored_leaves_ == num_splits + 1 && num_splits >= 1;
+  Log::Debug("device learner: next tree %s (allowed %d, rounds %d, scored early %d/%d)", spec_ok ? "launched" : "not launched",
+             spec_allowed_ ? 1 : 0, rounds ? 1 : 0, early_scored_leaves_, num_splits + 1);
+  if (spec_ok) LaunchSpeculative();
+  return tree.release();
+}
+
+// this tree's arguments: the per-node masks, the extra_trees generator states, the bag
+dev::KArgs GPUTreeLearner::PrepareTreeArgs() {
   dev::KArgs a = args_;
   const bool bynode = config_->feature_fraction_bynode < 1.0;
   const bool bynode_ic = bynode && col_sampler_.has_interaction_constraints();
@@ -1272,13 +1293,12 @@ Tree* GPUTreeLearner::TrainDeviceMode(bool speculated) {
     a.root_identity = 1;
     root_rows_ = num_data_;
   }
-  last_stats_.rounds = 0;
-  last_stats_.expansions = 0;
-  last_stats_.graph = false;
-  last_stats_.speculated = speculated;
-  const bool can_round = RoundGrowth(a);
-  const bool rounds = can_round && AutoGrowthRounds();
-  const auto t_grow = std::chrono::steady_clock::now();
+  return a;
+}
+
+// the growth itself, in rounds or one split per step: the tree's split count; its records are in
+// h_rec_ / h_tree_out_ (rounds) or copied to h_rec_ (steps)
+int GPUTreeLearner::GrowTree(const dev::KArgs& a, bool rounds, bool speculated) {
   if (!rounds && last_tree_rounds_) {
     // one split per step after round trees: splittable rows follow the leaf ids again
     std::vector<dev::Leaf> lv(config_->num_leaves);
@@ -1329,8 +1349,10 @@ Tree* GPUTreeLearner::TrainDeviceMode(bool speculated) {
     }
     if (use_graph) {
       const int root_mode = (root_from_parts_ && !use_bag_) ? 1 : 0;
+      // (the extra_trees and by-node kernels are part of the graph)
+      const int graph_key = (a.xt_base != nullptr ? 1 : 0) + (a.bynode_rng != nullptr ? 2 : 0);
       if (graph_exec_ == nullptr || graph_rows_ != a.num_rows || graph_identity_ != a.root_identity ||
-          graph_root_mode_ != root_mode || graph_xt_ != (xt ? 1 : 0) + (bynode_ic ? 2 : 0)) {
+          graph_root_mode_ != root_mode || graph_xt_ != graph_key) {
         if (dcomm != nullptr) dcomm->HostBarrier();
         DestroyStepGraph();  // (the round graphs stay: the growth mode may switch per tree)
         hipGraph_t g = nullptr;
@@ -1356,7 +1378,7 @@ Tree* GPUTreeLearner::TrainDeviceMode(bool speculated) {
           graph_rows_ = a.num_rows;
           graph_identity_ = a.root_identity;
           graph_root_mode_ = root_mode;
-          graph_xt_ = (xt ? 1 : 0) + (bynode_ic ? 2 : 0);  // (the by-node kernels are part of the graph)
+          graph_xt_ = graph_key;
         }
       }
       if (graph_exec_ != nullptr) {
@@ -1376,16 +1398,13 @@ Tree* GPUTreeLearner::TrainDeviceMode(bool speculated) {
     }
     num_splits = h_step_->nsplit;
   }
-  if (can_round) {
-    AutoGrowthRecord(std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_grow).count());
-  }
-  last_stats_.device_mode = true;
-  last_stats_.splits = num_splits;
-  // every step's collectives run (exiting early once the tree is done): the sequence is fixed
-  if (!rounds) {
-    last_stats_.collective_bytes =
-        distributed_ ? root_collective_bytes_ + split_collective_bytes_ * (config_->num_leaves - 1) : 0.0;
-  }
+  return num_splits;
+}
+
+// the host generators catch up with the draws the device made: per-node samples, extra_trees
+// thresholds (voting: the global scans' too)
+void GPUTreeLearner::ReplayHostGenerators(const dev::KArgs& a, bool rounds, int num_splits) {
+  const bool bynode = a.node_mask != nullptr, bynode_ic = a.bynode_rng != nullptr, xt = a.xt_base != nullptr;
   if (bynode && rounds) {
     // round growth: the draws the replay counted (Round::bynode_next), the root's included
     // when the root was scanned (0 otherwise: the root plan decides from the global count)
@@ -1421,27 +1440,9 @@ Tree* GPUTreeLearner::TrainDeviceMode(bool speculated) {
     }
   }
   if (xt && a.xt_cum_glob != nullptr) VoteXtAdvance();
-  if (a.ktrace != nullptr && !rounds) ReportKernelTrace(num_splits);
-  if (const char* kp = tuning::Get(tuning::Knob::KernelProbe)) {
-    if (kp[0] == '1' && !rounds) KernelFloorProbe(a);
-  }
-  // the promised training-score update (ExpectTrainingScoreUpdate), on the device before the
-  // host builds the tree
-  // round growth: the tree's last plan wrote the split records to the host (KArgs::host_out),
-  // or they are copied now (one record per split) and the host waits for that copy only
-  const double shrink = train_shrink_;
-  const dev::SplitRecord* recs = h_rec_;
-  const bool copy_recs = rounds && num_splits > 0 && !tree_out_used_;
-  if (rounds && tree_out_used_) recs = reinterpret_cast<const dev::SplitRecord*>(h_tree_out_ + dev::kHostOutHeaderWords);
-  if (copy_recs) {
-    HIPCHECK(hipMemcpyAsync(h_rec_, d_rec_, sizeof(dev::SplitRecord) * num_splits, hipMemcpyDeviceToHost, stream_));
-    if (rec_event_ == nullptr) HIPCHECK(hipEventCreateWithFlags(&rec_event_, hipEventDisableTiming));
-    HIPCHECK(hipEventRecord(rec_event_, stream_));
-  }
-  if (shrink != 0.0 && num_splits >= 1 && FusedScoreWalk(num_splits + 1, 0) && !tuning::Off(tuning::Knob::EarlyScore)) {
-    EarlyScoreUpdate(num_splits, shrink);
-  }
-  if (copy_recs) HIPCHECK(hipEventSynchronize(rec_event_));
+}
+
+Tree* GPUTreeLearner::TreeFromRecords(const dev::SplitRecord* recs, int num_splits) const {
   common::ScopedTimer build_timer("GPUTreeLearner::BuildTree");
   const bool track = !config_->interaction_constraints_vector.empty();
   std::unique_ptr<Tree> tree(new Tree(config_->num_leaves, track));
@@ -1474,11 +1475,6 @@ Tree* GPUTreeLearner::TrainDeviceMode(bool speculated) {
     Log::Warning("No further splits with positive gain, best gain: %f", -std::numeric_limits<double>::infinity());
   }
   Log::Debug("Trained a tree with leaves = %d and max_depth = %d", tree->num_leaves(), tree->max_depth());
-  // the records are consumed: the next tree may be launched now (its last plan rewrites them)
-  const bool spec_ok = SpeculationEligible(a, rounds) && early_scored_leaves_ == num_splits + 1 && num_splits >= 1;
-  Log::Debug("device learner: next tree %s (allowed %d, rounds %d, scored early %d/%d)", spec_ok ? "launched" : "not launched",
-             spec_allowed_ ? 1 : 0, rounds ? 1 : 0, early_scored_leaves_, num_splits + 1);
-  if (spec_ok) LaunchSpeculative();
   return tree.release();
 }
 
@@ -1486,16 +1482,10 @@ Tree* GPUTreeLearner::TrainDeviceMode(bool speculated) {
 // calls can change its inputs: GBDT allowed it (plain boosting, no bagging / renewal / custom
 // gradients, one model per iteration), this tree's score walk computes the next gradients, and
 // the tree grows in rounds of a single process without per-tree host state (per-node samples,
-// extra_trees draws, CEGB, forced splits, intermediate monotone, the timing probe).
-bool GPUTreeLearner::SpeculationEligible(const dev::KArgs& a, bool rounds) const {
-  if (!spec_allowed_ || !rounds || distributed_ || use_bag_ || !device_mode_) return false;
-  if (!tuning::On(tuning::Knob::Speculate)) return false;  // (opt-in: profiles/r06_speculation_ab.md)
-  if (a.host_out == nullptr && !tree_out_used_) return false;
-  if (config_->feature_fraction_bynode < 1.0 || config_->extra_trees || CostEffectiveGB::Enabled(*config_)) return false;
-  if (a.forced_n > 0 || a.p.mono_inter || a.ktrace != nullptr) return false;
-  if (auto_state_ != kAutoRounds || num_tree_per_iteration_ != 1) return false;
-  return true;
-}
+// extra_trees draws, CEGB, forced splits, intermediate monotone, the timing probe): the plan's
+// may_speculate, asked again with the facts as the grown tree left them (whether its records came
+// through host_out, what the timing settled on; opt-in: profiles/r06_speculation_ab.md).
+bool GPUTreeLearner::SpeculationEligible() const { return PlanGrowth(*config_, Facts()).may_speculate; }
 
 void GPUTreeLearner::LaunchSpeculative() {
   common::ScopedTimer timer("GPUTreeLearner::LaunchSpeculative");

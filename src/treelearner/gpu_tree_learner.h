@@ -1,15 +1,17 @@
 // MI355X tree learner: host orchestration of the HIP kernels in src/device/.
 //
-// Two growth modes share the same HBM state (row-major bin matrix, packed gradients,
+// Two residencies share the same HBM state (row-major bin matrix, packed gradients,
 // partition indices, histogram pool):
 //  * device-resident (default): the whole tree -- split selection included -- runs as
-//    a fixed kernel sequence on one stream (optionally replayed from a hipGraph); the
-//    host reads the split records back once per tree.
+//    kernels on one stream (replayed from hipGraphs); the host reads the split records
+//    back once per tree.  Forced splits, interaction constraints, extra_trees, per-node
+//    column sampling, CEGB, monotone constraints and all four learner kinds grow this way.
+//    The tree grows in rounds (up to round_k_ leaves expanded at once) or one split per step.
 //  * host-assisted: the SerialTreeLearner loop runs on the host and only histogram
-//    construction, row partitioning and leaf sums are offloaded.  Used for features the
-//    device split scan does not implement (forced splits, interaction constraints,
-//    extra_trees, per-node column sampling, CEGB, categorical features with > 1024
-//    categories) and under the voting-parallel learner.
+//    construction, row partitioning and leaf sums are offloaded.
+// Which of these a tree takes, what round growth replays and whether the next tree may be
+// launched early is decided by the one rule list of growth_plan.cpp (PlanGrowth); DecideMode
+// asks it before every tree and logs why a tree is host-assisted.
 // The reference's GPU learner (src/treelearner/gpu_tree_learner.cpp, OpenCL) offloads
 // only the histogram build; this learner keeps the training scores, gradients and the
 // data partition resident on the device across iterations.
@@ -26,6 +28,7 @@
 #include "../device/kernels.h"
 #include "../device/rank_tables.h"
 #include "lgbm_amd/device_learner.h"
+#include "growth_plan.h"
 #include "lgbm_amd/tuning.h"
 #include "serial_tree_learner.h"
 
@@ -38,7 +41,7 @@ class GPUTreeLearner : public SerialTreeLearner, public DeviceTreeLearner {
   // rows and builds / scans only its own features (feature_parallel_tree_learner.cpp)
   // voting: rows sharded; each rank scans its local histograms, the ranks elect top_k features
   // per leaf and only their histograms are summed (reference voting_parallel_tree_learner.cpp)
-  enum class Mode { kSerial, kData, kFeature, kVoting };
+  using Mode = LearnerKind;
   GPUTreeLearner(const Config* config, Mode mode);
   explicit GPUTreeLearner(const Config* config) : GPUTreeLearner(config, Mode::kSerial) {}
   // host-assisted growth for every tree (the voting-parallel learner scans on the host)
@@ -109,8 +112,18 @@ class GPUTreeLearner : public SerialTreeLearner, public DeviceTreeLearner {
   void UploadData();
   void FreeAll();
   void FreeBuffers();
+  // the growth rules' facts as the learner has them now, and their answer for this tree
+  GrowthFacts Facts() const;
   void DecideMode();
+  GrowthPlan plan_;
+  ForcedSplits forced_state_ = ForcedSplits::kNone;  // (SetupForcedSplits, as DecideMode called it)
+  // a device-resident tree: its per-tree arguments, the growth (its split count), the host
+  // generators caught up with the device's draws, the Tree of the split records
   Tree* TrainDeviceMode(bool speculated = false);
+  dev::KArgs PrepareTreeArgs();
+  int GrowTree(const dev::KArgs& a, bool rounds, bool speculated);
+  void ReplayHostGenerators(const dev::KArgs& a, bool rounds, int num_splits);
+  Tree* TreeFromRecords(const dev::SplitRecord* recs, int num_splits) const;
   void EnqueueTree(const dev::KArgs& a);
   void DestroyGraph();
   void KernelFloorProbe(const dev::KArgs& a);
@@ -144,11 +157,9 @@ class GPUTreeLearner : public SerialTreeLearner, public DeviceTreeLearner {
   T* Alloc(size_t n);
 
   // round growth (speculative multi-leaf expansion, src/device/round_kernels.hip): up to
-  // round_k_ leaves expanded per round; trees whose split order depends on more than each
-  // leaf's own rows (per-node sampling, extra_trees draws, CEGB, forced splits) and the
-  // distributed learners grow one split per step
-  bool RoundGrowth(const dev::KArgs& a) const;
-  bool CegbRounds(const dev::KArgs& a) const;  // CEGB penalties on round growth (this tree)
+  // round_k_ leaves expanded per round; whether this tree may (plan_.growth)
+  bool RoundGrowth() const;
+  bool CegbRounds() const;  // Growth::kRoundsOnceSampleUsed, resolved for this tree
   int RunRounds(dev::KArgs a);  // the tree's splits; h_rec_ holds their records
   struct RoundLaunch {  // a launched round tree (LaunchRounds), as its wait needs it
     dev::KArgs a{};
@@ -165,7 +176,7 @@ class GPUTreeLearner : public SerialTreeLearner, public DeviceTreeLearner {
   // through GBDT.  The next Train() only waits for it if its inputs are the ones the launch
   // assumed (the walk's gradients, nothing reset); otherwise the launched tree is drained and
   // the tree grown again with the same feature sample.
-  bool SpeculationEligible(const dev::KArgs& a, bool rounds) const;
+  bool SpeculationEligible() const;
   void LaunchSpeculative();
   void DropSpeculation();  // drain a launched next tree, restore the column sampler
   bool spec_allowed_ = false;
@@ -264,7 +275,7 @@ class GPUTreeLearner : public SerialTreeLearner, public DeviceTreeLearner {
   // voting rounds: proposals of every child of the round -> allgather -> elections + elected
   // local histograms -> all-reduce (one of each per round)
   void RoundVoteExchange(const dev::KArgs& glob);
-  bool distributed_ = false;    // kData / kFeature on more than one rank
+  bool distributed_ = false;    // kData / kFeature / kVoting on more than one rank
   int world_ = 1, rank_ = 0;
   // feature ownership (distributed): storage-group blocks balanced by bins (SetupOwnership);
   // data-parallel with feature_fraction < 1: re-assigned per tree over the used groups
@@ -286,6 +297,7 @@ class GPUTreeLearner : public SerialTreeLearner, public DeviceTreeLearner {
   int owned_bin_lo_ = 0;
   int rs_block_ = 0;            // padded owner block, histogram bins
   int num_cat_total_ = 0;
+  int max_cat_bins_ = 0;        // the largest categorical feature's num_bin
   int32_t* d_feat_list_ = nullptr;
   int32_t* d_fb_index_ = nullptr;
   int32_t* d_rs_pos_ = nullptr;

@@ -493,6 +493,46 @@ def test_voting_local_scan_interaction_constraints(world, growth, gpu_available,
                 assert a[k] == b.get(k), "tree %d: %s" % (i, k)
 
 
+@pytest.mark.parametrize("learner,extra,device,rounds", [
+    ("data", {"feature_fraction_bynode": 0.6}, True, True),
+    ("voting", {"extra_trees": True, "extra_seed": 7, "top_k": 4}, False, False),
+], ids=["data_bynode", "voting_extra_trees_categorical"])
+def test_growth_plan_matches_distributed_growth(learner, extra, device, rounds, gpu_available, monkeypatch, tmp_path):
+    """LGBM_AMD_GrowthPlan against two thread ranks (tests/test_gpu_learner.py::
+    test_growth_plan_matches_growth has the single-process modes): data-parallel per-node sampling
+    grows device-resident in rounds, voting extra_trees with a categorical feature host-assisted;
+    every tree of every rank, from the iteration logs."""
+    import json
+    from growth_facts import learner_plan
+    rng = np.random.RandomState(31)
+    n = 4096
+    X = rng.randn(n, 8).astype(np.float32)
+    X[:, 5] = rng.randint(0, 6, size=n)
+    y = (X[:, 0] + X[:, 1] * X[:, 2] - 0.5 * (X[:, 5] == 3) + 0.3 * rng.randn(n) > 0).astype(np.float32)
+    base = {"objective": "binary", "num_leaves": 15, "max_bin": 15, "min_data_in_leaf": 5, "verbose": -1,
+            "device_type": "gpu", "seed": 3, "max_cat_to_onehot": 8, "boost_from_average": False}
+    params = dict(base, tree_learner=learner, num_machines=2, pre_partition=True, **extra)
+    full = lgb.Dataset(X, y, params=base, categorical_feature=[5], free_raw_data=False).construct()
+    log = tmp_path / "iters.jsonl"
+    monkeypatch.setenv("LGBM_AMD_ITER_LOG", str(log))
+
+    def rank_fn(r):
+        lgb.train(params, full.subset(np.arange(r, n, 2)), 3, categorical_feature=[5])
+
+    with ThreadRanks(2, timeout_s=120, device_comm=True) as tr:
+        res = tr.run(rank_fn)
+    assert all(r.ok for r in res), [str(r.error) for r in res]
+    plan = learner_plan(params, kind=learner, world=2, device_comm=True, num_features=8, num_categorical=1,
+                        max_cat_bins=6, total_bins=8 * 15, forced="none")
+    assert (plan["device_resident"], plan["growth"] == "rounds") == (device, rounds), plan
+    for r in range(2):
+        rows = [json.loads(line) for line in (tmp_path / ("iters.jsonl.rank%d" % r)).read_text().splitlines()]
+        assert len(rows) == 3
+        for row in rows:
+            assert row["device_resident"][0] == plan["device_resident"], (plan, row)
+            assert (row["rounds"][0] > 0) == (plan["growth"] == "rounds"), (plan, row)
+
+
 def test_bench_py_under_torchrun_two_processes(gpu_available, tmp_path):
     """The multi-GPU benchmark entry point as the driver launches it (torch.distributed.run,
     one process per rank, peer comm), here with 2 processes sharing the box's GPU and 1M rows:

@@ -1140,3 +1140,59 @@ def test_training_auc_with_float_colliding_scores(variants, gpu_available, monke
     monkeypatch.setenv("LGBM_AMD_HOST_METRICS", "1")
     host = run()
     np.testing.assert_allclose(dev, host, rtol=1e-12, atol=0)
+
+
+_GROWTH_CASES = [
+    # (id, parameters, environment, categorical column declared, facts beside the data's)
+    ("plain", {}, {}, True, {}),
+    ("bynode", {"feature_fraction_bynode": 0.6}, {}, True, {}),
+    ("bynode_ic", {"feature_fraction_bynode": 0.6, "interaction_constraints": [[0, 1, 2, 5], [3, 4, 5, 6], [1, 6, 7]]},
+     {}, True, {}),
+    ("extra_trees", {"extra_trees": True, "extra_seed": 7}, {}, True, {}),
+    ("extra_trees_no_categorical", {"extra_trees": True, "extra_seed": 7}, {}, False, {}),
+    ("cegb_split", {"cegb_penalty_split": 1e-4}, {}, True, {}),
+    ("cegb_coupled", {"cegb_penalty_feature_coupled": [0.5, 0.1, 0.3, 0, 0.2, 0.1, 0.4, 0], "cegb_tradeoff": 0.8},
+     {}, True, {}),
+    ("cegb_lazy", {"cegb_penalty_feature_lazy": [1e-4, 2e-4, 0, 1e-4, 0, 3e-4, 1e-4, 0]}, {}, True, {}),
+    ("forced_splits", {"forcedsplits_filename": "forced.json"}, {}, True, {"forced": "scheduled"}),
+    ("intermediate_monotone", {"monotone_constraints": [1, -1, 0, 0, 0, 0, 0, 0],
+                               "monotone_constraints_method": "intermediate"}, {}, True, {}),
+    ("host_assist", {}, {"LGBM_AMD_HOST_ASSIST": "1"}, True, {"force_host": True}),
+    ("round_k_1", {}, {"LGBM_AMD_ROUND_K": "1"}, True, {"round_k_knob": 1}),
+]
+
+
+@pytest.mark.parametrize("params,env,cat,facts", [c[1:] for c in _GROWTH_CASES], ids=[c[0] for c in _GROWTH_CASES])
+def test_growth_plan_matches_growth(params, env, cat, facts, gpu_available, monkeypatch, tmp_path):
+    """What LGBM_AMD_GrowthPlan answers for a learner's parameters and facts is how the learner
+    grows: every tree's residency and whether it grew in rounds, from the iteration log.  Coupled
+    CEGB penalties outside the round replay grow in rounds once the tree's sample is used up: the
+    first tree, with nothing used yet, takes one split per step."""
+    from helpers.growth_facts import learner_plan
+    rng = np.random.RandomState(31)
+    n = 4096
+    X = rng.randn(n, 8).astype(np.float32)
+    X[:, 5] = rng.randint(0, 6, size=n)
+    y = (X[:, 0] + X[:, 1] * X[:, 2] - 0.5 * (X[:, 5] == 3) + 0.3 * rng.randn(n) > 0).astype(np.float32)
+    params = dict({"objective": "binary", "num_leaves": 15, "max_bin": 15, "min_data_in_leaf": 5, "verbose": -1,
+                   "device_type": "gpu", "seed": 3, "max_cat_to_onehot": 8}, **params)
+    if "forcedsplits_filename" in params:
+        path = tmp_path / "forced.json"
+        path.write_text(json.dumps({"feature": 0, "threshold": 0.1, "left": {"feature": 1, "threshold": -0.2}}))
+        params["forcedsplits_filename"] = str(path)
+    log = tmp_path / "iters.jsonl"
+    monkeypatch.setenv("LGBM_AMD_ITER_LOG", str(log))
+    for k, v in env.items():
+        monkeypatch.setenv(k, v)
+    ds = lgb.Dataset(X, y, params=params, categorical_feature=[5] if cat else [])
+    lgb.train(params, ds, 3, verbose_eval=False)
+    rows = [json.loads(line) for line in log.read_text().splitlines()]
+    assert len(rows) == 3
+    plan = learner_plan(params, num_features=8, num_categorical=1 if cat else 0, max_cat_bins=6 if cat else 0,
+                        total_bins=8 * 15, **facts)
+    print(plan, [(r["device_resident"][0], r["rounds"][0]) for r in rows])
+    if plan["growth"] == "rounds_once_sample_used":
+        rows, plan = rows[:1], dict(plan, growth="steps")
+    for r in rows:
+        assert r["device_resident"][0] == plan["device_resident"], (plan, r)
+        assert (r["rounds"][0] > 0) == (plan["growth"] == "rounds"), (plan, r)

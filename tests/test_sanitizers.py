@@ -61,6 +61,21 @@ def test_examples_clean_under_asan_ubsan(tmp_path, asan_cli, example_data, examp
     assert (tmp_path / "m.txt").exists()
 
 
+GROWTH_DRIVER = os.path.join(ROOT, "build_asan", "growth_plan_driver")
+
+
+def test_growth_plan_clean_under_asan_ubsan(host_only):
+    """The device learner's growth rules and the JSON glue of LGBM_AMD_GrowthPlan
+    (src/treelearner/growth_plan.cpp, plain C++) with a few rows of tests/test_growth_plan.py's
+    table (tests/native/growth_plan_driver.cpp), as a stand-alone instrumented program."""
+    _build("build_asan/growth_plan_driver", GROWTH_DRIVER)
+    env = dict(os.environ, ASAN_OPTIONS="detect_leaks=1:abort_on_error=0", UBSAN_OPTIONS="print_stacktrace=1")
+    out = subprocess.run([GROWTH_DRIVER], env=env, capture_output=True, text=True, timeout=60)
+    log = out.stdout + out.stderr
+    assert out.returncode == 0 and "growth plan driver ok" in log, log[-4000:]
+    assert "AddressSanitizer" not in log and "runtime error" not in log, log[-4000:]
+
+
 TSAN_DRIVER = os.path.join(ROOT, "build_tsan", "tsan_driver")
 
 
