@@ -92,6 +92,9 @@ class GBDT {
   void Train(int snapshot_freq, const std::string& model_output_path);
   virtual bool TrainOneIter(const score_t* gradients, const score_t* hessians);
   virtual void RollbackOneIter();
+  // new leaf values for every tree from the training data's leaf matrix (row-major
+  // [nrow][ncol], one column per tree: the C API's layout); the vector form wraps it
+  void RefitTree(const int32_t* tree_leaf_prediction, int32_t nrow, int32_t ncol);
   void RefitTree(const std::vector<std::vector<int>>& tree_leaf_prediction);
   virtual bool EvalAndCheckEarlyStopping();
   int GetCurrentIteration() const { return static_cast<int>(models_.size()) / num_tree_per_iteration_; }
@@ -210,6 +213,8 @@ class GBDT {
   void TrainScoreMultiply(double v, int tree_id);
   void TrainScoreAddTree(const Tree* tree, int tree_id);
   double* HostTrainScore();
+  // RefitTree on the device learner (one process); false: the learner can not, nothing changed
+  bool RefitTreeOnDevice(const int32_t* leaf_pred, int32_t nrow, int32_t ncol);
   void MarkHostScoreStale() { host_score_fresh_ = false; }
   // run the bagging pass over all rows with `helper`, filling bag_data_indices_
   data_size_t RunBagging(const std::function<data_size_t(data_size_t, data_size_t, data_size_t*)>& helper);

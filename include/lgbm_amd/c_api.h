@@ -266,6 +266,14 @@ LIGHTGBM_C_EXPORT int LGBM_AMD_CsrToSlots(BoosterHandle handle, const void* indp
                                           const int32_t* indices, const void* data, int data_type, int64_t nindptr,
                                           int64_t nelem, int start_iteration, int num_iteration,
                                           int32_t* out_num_used, int32_t* out_used, void* out_matrix);
+// the per-leaf sums of a device refit, evaluated on the host with the kernel's fixed-point rule
+// (src/device/refit_quant.h; no GPU needed): leaf[n] in [0, num_leaves) (anything else is an
+// error), grad / hess[n]; out_sums[2 * num_leaves] receives sum g then sum h per leaf
+// (dequantised), out_counts[num_leaves] the rows per leaf, out_scale_exp[2] the exponents e of
+// the two scales 2^e.  A sum is within count * 2^-(e + 1) of the exact sum of its fp32 inputs
+LIGHTGBM_C_EXPORT int LGBM_AMD_RefitLeafSums(const int32_t* leaf, const float* grad, const float* hess, int64_t n,
+                                             int32_t num_leaves, double* out_sums, int64_t* out_counts,
+                                             int32_t* out_scale_exp);
 // the device learner's growth rules evaluated on the host (no GPU, no dataset): how a learner
 // with these training parameters and these facts (a JSON object of GrowthFacts' fields,
 // src/treelearner/growth_plan.h; absent ones keep their defaults, environment knobs are facts

@@ -96,6 +96,35 @@ class DeviceTreeLearner {
     return false;
   }
 
+  // ---- refit of an existing forest's leaf values (GBDT::RefitTree) from the leaf matrix
+  // (row-major int32 [nrow][ncol], one column per tree): no bins, thresholds or tree walks.
+  // Each returns false where the learner can not do it (the caller keeps its host path).
+  //
+  // Stage a window of the matrix's columns, from column `col0` on, tree-major on the device,
+  // checking every entry against its tree's leaf count (num_leaves[ncol]); *cols_staged is the
+  // window's width, chosen from the free device memory (or LGBM_AMD_REFIT_WINDOW, counted in
+  // iterations of trees_per_iteration columns).  An entry outside its tree is a fatal error that
+  // names the tree, raised before anything reads the staged ids.  leaf == nullptr releases the
+  // staged window
+  virtual bool RefitStageWindow(const int32_t* leaf, int64_t nrow, int ncol, int col0, const int* num_leaves,
+                                int trees_per_iteration, int* cols_staged) {
+    (void)leaf; (void)nrow; (void)ncol; (void)col0; (void)num_leaves; (void)trees_per_iteration; (void)cols_staged;
+    return false;
+  }
+  // per-leaf sums of class `tree_id`'s device gradients / hessians and the row counts over staged
+  // column `col` (an index into the matrix): exact fixed-point sums (src/device/refit_quant.h)
+  // dequantised here; scale_exp[2]: the exponents of the two scales
+  virtual bool RefitLeafSums(int col, int tree_id, int num_leaves, double* sum_g, double* sum_h, data_size_t* count,
+                             int* scale_exp) {
+    (void)col; (void)tree_id; (void)num_leaves; (void)sum_g; (void)sum_h; (void)count; (void)scale_exp;
+    return false;
+  }
+  // score[i] += values[leaf[i]] on the training scores of class `tree_id`, over staged column `col`
+  virtual bool RefitAddLeafValues(int col, int tree_id, const double* values, int num_leaves) {
+    (void)col; (void)tree_id; (void)values; (void)num_leaves;
+    return false;
+  }
+
   // test support (tests/test_gpu_kernels.py): the state the last device-grown tree left in HBM.
   // A leaf's rows (partition), its raw fixed-point histogram slot, which histogram bins are
   // meaningful (the slices of features evaluated for the leaf: a feature its parent could not

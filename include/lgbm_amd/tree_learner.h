@@ -39,4 +39,10 @@ class TreeLearner {
                                         const Config* config);
 };
 
+// a copy of old_tree with its leaf values refitted from per-leaf (sum g, sum h, count): the one
+// formula of TreeLearner::FitByExistingTree and the device refit (serial_tree_learner.cpp).
+// sum_h includes the kEpsilon the reference's hessian sums start from
+Tree* RefitLeafOutputs(const Tree* old_tree, const Config& config, const double* sum_g, const double* sum_h,
+                       const data_size_t* count);
+
 }  // namespace lgbm_amd

@@ -51,6 +51,7 @@ constexpr int kQueryMetricDeviceMaxDocs = 16384;
   X(HostMetrics, "LGBM_AMD_HOST_METRICS", "1: metrics evaluated on the host")                                  \
   X(HostRenew, "LGBM_AMD_HOST_RENEW", "1: percentile leaf renewal on the host")                                \
   X(HostPredict, "LGBM_AMD_HOST_PREDICT", "1: C API prediction on the host")                                   \
+  X(HostRefit, "LGBM_AMD_HOST_REFIT", "1: a device booster refits with the CPU learner and a tree walk of the scores")  \
   X(HostSparse, "LGBM_AMD_HOST_SPARSE", "0/1: dense / sparse host storage of every group")                     \
   X(DeviceBinning, "LGBM_AMD_DEVICE_BINNING", "0/1: value-to-bin on the host / the GPU")                       \
   X(NoGraph, "LGBM_AMD_NO_GRAPH", "1: kernels launched eagerly instead of from hipGraphs")                     \
@@ -77,6 +78,8 @@ constexpr int kQueryMetricDeviceMaxDocs = 16384;
   X(HistRowsCap, "LGBM_AMD_HIST_ROWS_CAP", "n: rows per partial histogram block")                              \
   X(TextBlockBytes, "LGBM_AMD_TEXT_BLOCK_BYTES", "n: text reader block size (tests)")                          \
   X(PredictChunkRows, "LGBM_AMD_PREDICT_CHUNK_ROWS", "n: rows per chunk of a device prediction (tests; auto from free memory)")  \
+  X(RefitWindow, "LGBM_AMD_REFIT_WINDOW", "n: iterations per staged window of a device refit (tests; auto from free memory)")  \
+  X(RefitWide, "LGBM_AMD_REFIT_WIDE", "1: a device refit stages leaf ids as int32 (tests; auto above 65536 leaves)")  \
   /* tuning (same models; defaults above) */                                                                   \
   X(RoundK, "LGBM_AMD_ROUND_K", "n: expansions per round, fixed (1: one split per step)")                      \
   X(RoundVmax, "LGBM_AMD_ROUND_VMAX", "n: speculation depth below a leaf (14)")                                \

@@ -1181,7 +1181,10 @@ class Booster:
         if self._objective_none:
             raise LightGBMError("Cannot refit due to null objective function.")
         pred = self._to_predictor(copy.deepcopy(kwargs))
+        # (predict hands the leaf indices over as int32, row-major [nrow, trees]: the layout
+        # LGBM_BoosterRefit takes, with no further conversion; one tree gives a 1-d result)
         leaves = pred.predict(data, -1, pred_leaf=True)
+        leaves = leaves.reshape(-1, self.num_trees())
         nrow, ncol = leaves.shape
         params = copy.deepcopy(self.params)
         params["refit_decay_rate"] = decay_rate

@@ -19,6 +19,10 @@ the kernels can be checked one by one against plain PyTorch references
 * :func:`forest_predict` -- a trained booster's raw scores, leaf indices or SHAP
   contributions of a matrix that already is on the GPU (src/device/predict_kernels.hip,
   src/device/shap_kernels.hip; reference gbdt_prediction.cpp, Tree::TreeSHAP)
+* :func:`leaf_sums` / :func:`add_leaf_values` -- the two per-tree passes of a device refit
+  (src/device/refit_kernels.hip; reference SerialTreeLearner::FitByExistingTree): exact
+  fixed-point per-leaf sums of gradients and hessians over a column of leaf indices, and
+  ``score += values[leaf]``; :func:`refit_launch_info` gives their launch shape
 
 There is no host fallback: the ops need a GPU and the in-tree library.
 """
@@ -29,7 +33,8 @@ import numpy as np
 from .._native import LightGBMError, call as _native_call, params_str as param_dict_to_str
 from ..basic import _load_lib
 
-__all__ = ["gradients", "metric", "sample_rows", "forest_predict"]
+__all__ = ["gradients", "metric", "sample_rows", "forest_predict", "leaf_sums", "add_leaf_values",
+           "refit_launch_info"]
 
 
 def _torch():
@@ -225,3 +230,56 @@ def forest_predict(booster, X, kind="raw", start_iteration=0, num_iteration=-1):
                                        ctypes.c_int(start), ctypes.c_int(num), _dev_ptr(out, torch.float64, "out"),
                                        ctypes.c_int64(out.numel())))
     return out
+
+
+def refit_launch_info():
+    """The launch shape of the refit kernels: ``lds_leaves`` (the most leaves whose sums a
+    workgroup keeps in LDS; trees with more add straight to the global table), ``max_grid`` /
+    ``block`` / ``unroll`` of the leaf-sum pass (a thread's ``unroll`` rows in flight are
+    ``grid * block`` apart, so more than ``max_grid * block * unroll`` rows make it loop) and
+    ``value_lds_leaves`` (the most leaf values the score update stages in LDS)."""
+    out = (ctypes.c_int64 * 5)()
+    _check(_lib().LGBMAMD_OpRefitLaunchInfo(out))
+    return {"lds_leaves": out[0], "max_grid": out[1], "block": out[2], "unroll": out[3], "value_lds_leaves": out[4]}
+
+
+def leaf_sums(leaf, grad, hess, num_leaves):
+    """Per-leaf sums of ``grad`` and ``hess`` (float32 GPU tensors ``[n]``) and row counts over the
+    leaf indices ``leaf`` (int32 GPU tensor ``[n]``, every entry in ``[0, num_leaves)``; anything
+    else raises before a kernel uses it).
+
+    Returns ``(sum_g, sum_h, count, scale_exp)``: float64 ``[num_leaves]`` GPU tensors, an int64
+    ``[num_leaves]`` GPU tensor and the exponents ``(e_g, e_h)`` of the fixed-point scales
+    ``2^e``.  Each row is rounded once to a multiple of ``2^-e`` and the integer sums are exact, so
+    a sum is within ``count * 2^-(e + 1)`` of the exact sum and the same on every run."""
+    torch = _torch()
+    n = leaf.numel()
+    if grad.numel() != n or hess.numel() != n:
+        raise LightGBMError("leaf, grad and hess must have the same length")
+    num_leaves = int(num_leaves)
+    sums = np.zeros(2 * max(num_leaves, 0), dtype=np.float64)
+    counts = np.zeros(max(num_leaves, 0), dtype=np.int64)
+    exps = (ctypes.c_int32 * 2)()
+    torch.cuda.synchronize(leaf.device)
+    _check(_lib().LGBMAMD_OpLeafSums(_dev_ptr(leaf, torch.int32, "leaf"), _dev_ptr(grad, torch.float32, "grad"),
+                                     _dev_ptr(hess, torch.float32, "hess"), ctypes.c_int64(n),
+                                     ctypes.c_int32(num_leaves), sums.ctypes.data_as(ctypes.POINTER(ctypes.c_double)),
+                                     counts.ctypes.data_as(ctypes.POINTER(ctypes.c_int64)), exps))
+    dev = leaf.device
+    return (torch.from_numpy(sums[:num_leaves].copy()).to(dev), torch.from_numpy(sums[num_leaves:].copy()).to(dev),
+            torch.from_numpy(counts).to(dev), (int(exps[0]), int(exps[1])))
+
+
+def add_leaf_values(score, leaf, values):
+    """``score[i] += values[leaf[i]]`` in place: ``score`` float64 GPU tensor ``[n]``, ``leaf``
+    int32 GPU tensor ``[n]`` with entries in ``[0, len(values))`` (anything else raises before a
+    kernel uses it), ``values`` float64 GPU tensor.  One double add per row; returns ``score``."""
+    torch = _torch()
+    n = score.numel()
+    if leaf.numel() != n:
+        raise LightGBMError("score and leaf must have the same length")
+    torch.cuda.synchronize(score.device)
+    _check(_lib().LGBMAMD_OpAddLeafValues(_dev_ptr(score, torch.float64, "score"), _dev_ptr(leaf, torch.int32, "leaf"),
+                                          _dev_ptr(values, torch.float64, "values"), ctypes.c_int64(n),
+                                          ctypes.c_int32(values.numel())))
+    return score

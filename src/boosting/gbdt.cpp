@@ -696,8 +696,92 @@ void GBDT::Train(int snapshot_freq, const std::string& model_output_path) {
 
 void GBDT::RefitTree(const std::vector<std::vector<int>>& leaf_pred) {
   LGBM_CHECK_GT(leaf_pred.size(), 0u);
-  LGBM_CHECK_EQ(static_cast<size_t>(num_data_), leaf_pred.size());
-  LGBM_CHECK_EQ(models_.size(), leaf_pred[0].size());
+  const size_t ncol = leaf_pred[0].size();
+  std::vector<int32_t> flat(leaf_pred.size() * ncol);
+  for (size_t i = 0; i < leaf_pred.size(); ++i) {
+    LGBM_CHECK_EQ(leaf_pred[i].size(), ncol);
+    std::copy(leaf_pred[i].begin(), leaf_pred[i].end(), flat.begin() + i * ncol);
+  }
+  RefitTree(flat.data(), static_cast<int32_t>(leaf_pred.size()), static_cast<int32_t>(ncol));
+}
+
+// The device learner's refit: per iteration the gradients are computed on the device (or
+// uploaded, for an objective without a device kernel); per tree the device sums (g, h, count)
+// per leaf over the tree's staged leaf column, the host turns the few sums into leaf values with
+// the CPU learner's formula (RefitLeafOutputs), and the device adds them to the scores over the
+// same column.  The new trees replace the old ones when every window has passed its checks: a
+// rejected leaf matrix leaves the booster as it was.
+bool GBDT::RefitTreeOnDevice(const int32_t* leaf_pred, int32_t nrow, int32_t ncol) {
+  const int ntpi = num_tree_per_iteration_;
+  const int num_iter = ncol / ntpi;
+  std::vector<int> num_leaves(ncol);
+  for (int c = 0; c < ncol; ++c) num_leaves[c] = models_[c]->num_leaves();
+  std::vector<std::unique_ptr<Tree>> fresh(ncol);
+  std::vector<double> saved;  // the scores before the first tree, kept while a later window may still be rejected
+  std::vector<double> sum_g, sum_h, values;
+  std::vector<data_size_t> count;
+  int staged_end = 0;
+  try {
+    for (int it = 0; it < num_iter; ++it) {
+      const int c0 = it * ntpi;
+      if (c0 >= staged_end) {
+        int staged = 0;
+        if (!device_learner_->RefitStageWindow(leaf_pred, nrow, ncol, c0, num_leaves.data(), ntpi, &staged)) {
+          if (it == 0) return false;
+          Log::Fatal("device refit: the leaf columns from tree %d on could not be staged", c0);
+        }
+        staged_end = c0 + staged;
+        if (it == 0 && staged_end < ncol) {
+          saved.resize(static_cast<size_t>(nrow) * ntpi);
+          for (int k = 0; k < ntpi; ++k) device_learner_->SyncScoreToHost(saved.data() + static_cast<size_t>(k) * nrow, k);
+        }
+      }
+      Boosting();
+      for (int k = 0; k < ntpi; ++k) {
+        const int mi = c0 + k;
+        const int nl = num_leaves[mi];
+        sum_g.resize(nl);
+        sum_h.resize(nl);
+        count.resize(nl);
+        values.resize(nl);
+        int scale_exp[2] = {0, 0};
+        if (!device_learner_->RefitLeafSums(mi, k, nl, sum_g.data(), sum_h.data(), count.data(), scale_exp)) {
+          Log::Fatal("device refit: no leaf sums for tree %d", mi);
+        }
+        for (int l = 0; l < nl; ++l) sum_h[l] = kEpsilon + sum_h[l];
+        fresh[mi].reset(RefitLeafOutputs(models_[mi].get(), *config_, sum_g.data(), sum_h.data(), count.data()));
+        for (int l = 0; l < nl; ++l) values[l] = fresh[mi]->LeafOutput(l);
+        if (!device_learner_->RefitAddLeafValues(mi, k, values.data(), nl)) {
+          Log::Fatal("device refit: the scores did not take tree %d", mi);
+        }
+        host_score_fresh_ = false;
+      }
+    }
+  } catch (...) {
+    int none = 0;
+    device_learner_->RefitStageWindow(nullptr, nrow, ncol, 0, num_leaves.data(), ntpi, &none);
+    for (int k = 0; k < ntpi && !saved.empty(); ++k) {
+      device_learner_->SyncScoreFromHost(saved.data() + static_cast<size_t>(k) * nrow, k);
+    }
+    host_score_fresh_ = false;
+    throw;
+  }
+  int none = 0;
+  device_learner_->RefitStageWindow(nullptr, nrow, ncol, 0, num_leaves.data(), ntpi, &none);
+  for (int c = 0; c < ncol; ++c) models_[c] = std::move(fresh[c]);
+  return true;
+}
+
+void GBDT::RefitTree(const int32_t* leaf_pred, int32_t nrow, int32_t ncol) {
+  LGBM_CHECK_GT(nrow, 0);
+  LGBM_CHECK_EQ(num_data_, nrow);
+  LGBM_CHECK_EQ(models_.size(), static_cast<size_t>(ncol));
+  // one process refits on the device (LGBM_AMD_HOST_REFIT=1: the branch below); distributed
+  // device learners keep the branch below
+  if (device_learner_ != nullptr && Network::num_machines() <= 1 && !tuning::On(tuning::Knob::HostRefit) &&
+      RefitTreeOnDevice(leaf_pred, nrow, ncol)) {
+    return;
+  }
   const int num_iter = static_cast<int>(models_.size()) / num_tree_per_iteration_;
   std::vector<int> lp(num_data_);
   for (int it = 0; it < num_iter; ++it) {
@@ -711,7 +795,7 @@ void GBDT::RefitTree(const std::vector<std::vector<int>>& leaf_pred) {
     for (int k = 0; k < num_tree_per_iteration_; ++k) {
       const int mi = it * num_tree_per_iteration_ + k;
       for (data_size_t i = 0; i < num_data_; ++i) {
-        lp[i] = leaf_pred[i][mi];
+        lp[i] = leaf_pred[static_cast<size_t>(i) * ncol + mi];
         LGBM_CHECK_LT(lp[i], models_[mi]->num_leaves());
       }
       const size_t off = static_cast<size_t>(k) * num_data_;

@@ -33,6 +33,7 @@
 #include "lgbm_amd/predictor.h"
 #include "lgbm_amd/random.h"
 #include "lgbm_amd/tuning.h"
+#include "../device/refit_quant.h"
 #include "../treelearner/growth_limits.h"
 
 using namespace lgbm_amd;
@@ -355,11 +356,7 @@ class Booster {
 
   void Refit(const int32_t* leaf_preds, int32_t nrow, int32_t ncol) {
     std::unique_lock<std::shared_mutex> l(mu_);
-    std::vector<std::vector<int32_t>> v(nrow, std::vector<int32_t>(ncol));
-    for (int32_t i = 0; i < nrow; ++i) {
-      for (int32_t j = 0; j < ncol; ++j) v[i][j] = leaf_preds[static_cast<size_t>(i) * ncol + j];
-    }
-    boosting_->RefitTree(v);
+    boosting_->RefitTree(leaf_preds, nrow, ncol);
   }
 
   bool TrainOneIter(const score_t* g, const score_t* h) {
@@ -1606,6 +1603,16 @@ int LGBM_AMD_CsrToSlots(BoosterHandle handle, const void* indptr, int indptr_typ
   API_BEGIN();
   static_cast<Booster*>(handle)->CsrToSlots(indptr, indptr_type, indices, data, data_type, nindptr, nelem,
                                             start_iteration, num_iteration, out_num_used, out_used, out_matrix);
+  API_END();
+}
+
+int LGBM_AMD_RefitLeafSums(const int32_t* leaf, const float* grad, const float* hess, int64_t n, int32_t num_leaves,
+                           double* out_sums, int64_t* out_counts, int32_t* out_scale_exp) {
+  API_BEGIN();
+  if (n < 0 || num_leaves <= 0) Log::Fatal("refit leaf sums: need n >= 0 rows and num_leaves > 0");
+  if (!dev::EvalRefitLeafSums(leaf, grad, hess, n, num_leaves, out_sums, out_counts, out_scale_exp)) {
+    Log::Fatal("refit leaf sums: a leaf id is outside [0, %d)", num_leaves);
+  }
   API_END();
 }
 

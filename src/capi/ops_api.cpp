@@ -5,8 +5,9 @@
 // (src/device/sample_kernels.hip), and with query sizes the listwise ranking gradients
 // (src/device/rank_kernels.hip) and the NDCG / MAP metrics -- callable one at a time so that
 // their numerics can be checked against plain PyTorch / NumPy references (tests/test_ops.py,
-// tests/test_rank_ops.py); and a booster's forest prediction (scores, leaf indices, SHAP
-// contributions) on a matrix that already is on the device.
+// tests/test_rank_ops.py); a booster's forest prediction (scores, leaf indices, SHAP
+// contributions) on a matrix that already is on the device; and the two per-tree passes of a
+// device refit (src/device/refit_kernels.hip: per-leaf sums, score update; tests/test_device_refit.py).
 //
 // Objectives and metrics are created from a parameter string exactly as training creates
 // them (reference objective_function.cpp:16-56, metric.cpp:16-63), so the kernels see the
@@ -21,6 +22,7 @@
 
 #include "../device/kernels.h"
 #include "../device/rank_tables.h"
+#include "../device/refit_quant.h"
 #include "lgbm_amd/c_api.h"
 #include "lgbm_amd/config.h"
 #include "lgbm_amd/dataset.h"
@@ -319,6 +321,110 @@ LIGHTGBM_C_EXPORT int LGBMAMD_OpMetric(const char* params, const float* label, c
     std::vector<double> h(nout, 0.0);
     OPCHECK(hipMemcpy(h.data(), a.out, sizeof(double) * nout, hipMemcpyDeviceToHost));
     give(m->FinishDevice(h));
+  });
+}
+
+namespace {
+
+// a caller's leaf ids (device, int32 [n]) as a staged column of a tree of num_leaves leaves
+// (uint16, or int32 above 65536 leaves), through the refit's staging kernel: every id is
+// checked there, and an id outside the tree is an error before any kernel indexes with it
+const void* StageLeafColumn(Scratch* sc, const int32_t* d_leaf, int64_t n, int32_t num_leaves, bool* wide) {
+  if (n < 0 || num_leaves <= 0) Log::Fatal("refit op: need n >= 0 rows and num_leaves > 0");
+  *wide = num_leaves > 65536;
+  void* column = sc->Alloc<char>(static_cast<size_t>(n) * (*wide ? sizeof(int32_t) : sizeof(uint16_t)));
+  const uint32_t flags0[2] = {0u, 0xffffffffu};
+  dev::RefitStageArgs a{};
+  tuning::PoisonArgs(&a);  // (every field set below)
+  a.src = d_leaf;
+  a.src_stride = 1;
+  a.rows = n;
+  a.row0 = 0;
+  a.num_rows = n;
+  a.cols = 1;
+  a.wide = *wide ? 1 : 0;
+  a.num_leaves = sc->Upload(&num_leaves, 1);
+  a.out = column;
+  a.bad = sc->Upload(flags0, 2);
+  dev::RefitStage(a, nullptr);
+  OPCHECK(hipGetLastError());
+  uint32_t bad = 0u;
+  OPCHECK(hipMemcpy(&bad, a.bad, sizeof(bad), hipMemcpyDeviceToHost));
+  if (bad != 0u) Log::Fatal("refit op: %u leaf ids are outside [0, %d)", bad, num_leaves);
+  return column;
+}
+
+}  // namespace
+
+// the launch shape of the refit kernels (tests size their inputs from it): out[0] the most
+// leaves whose sums a workgroup keeps in LDS, out[1] the most workgroups of the leaf-sum pass,
+// out[2] its threads per workgroup, out[3] rows in flight per thread (a thread's rows are
+// out[1] * out[2] apart), out[4] the most leaves whose values the score update stages in LDS
+LIGHTGBM_C_EXPORT int LGBMAMD_OpRefitLaunchInfo(int64_t* out) {
+  return Guard([&] {
+    out[0] = dev::kRefitLdsLeaves;
+    out[1] = dev::RefitSumGrid(int64_t(1) << 40);
+    out[2] = dev::kRefitThreads;
+    out[3] = dev::kRefitUnroll;
+    out[4] = dev::kRefitValueLdsLeaves;
+  });
+}
+
+// per-leaf sums of grad / hess (device, float32 [n]) and row counts over leaf ids (device, int32
+// [n]) with the refit's kernels (src/device/refit_kernels.hip): out_sums[2 * num_leaves] (host)
+// receives sum g then sum h, dequantised; out_counts[num_leaves]; out_scale_exp[2]
+LIGHTGBM_C_EXPORT int LGBMAMD_OpLeafSums(const int32_t* d_leaf, const float* d_grad, const float* d_hess, int64_t n,
+                                         int32_t num_leaves, double* out_sums, int64_t* out_counts,
+                                         int32_t* out_scale_exp) {
+  return Guard([&] {
+    Scratch sc;
+    bool wide = false;
+    const void* column = StageLeafColumn(&sc, d_leaf, n, num_leaves, &wide);
+    const size_t L = static_cast<size_t>(num_leaves);
+    dev::RefitSumArgs a{};
+    tuning::PoisonArgs(&a);  // (every field set below)
+    a.leaf = column;
+    a.wide = wide ? 1 : 0;
+    a.num_leaves = num_leaves;
+    a.n = n;
+    a.grad = d_grad;
+    a.hess = d_hess;
+    a.absmax = sc.Alloc<uint32_t>(2);
+    a.table = sc.Alloc<long long>(3 * L + 2);
+    dev::RefitLeafSums(a, nullptr);
+    OPCHECK(hipGetLastError());
+    std::vector<long long> t(3 * L + 2);
+    OPCHECK(hipMemcpy(t.data(), a.table, sizeof(long long) * t.size(), hipMemcpyDeviceToHost));
+    const int eg = static_cast<int>(t[3 * L]), eh = static_cast<int>(t[3 * L + 1]);
+    const double ig = dev::RefitScale(-eg), ih = dev::RefitScale(-eh);
+    for (size_t l = 0; l < L; ++l) {
+      out_sums[l] = static_cast<double>(t[l]) * ig;
+      out_sums[L + l] = static_cast<double>(t[L + l]) * ih;
+      out_counts[l] = t[2 * L + l];
+    }
+    out_scale_exp[0] = eg;
+    out_scale_exp[1] = eh;
+  });
+}
+
+// d_score[i] += d_values[leaf[i]] in place (device: float64 [n], int32 [n], float64 [num_leaves])
+LIGHTGBM_C_EXPORT int LGBMAMD_OpAddLeafValues(double* d_score, const int32_t* d_leaf, const double* d_values,
+                                              int64_t n, int32_t num_leaves) {
+  return Guard([&] {
+    Scratch sc;
+    bool wide = false;
+    const void* column = StageLeafColumn(&sc, d_leaf, n, num_leaves, &wide);
+    dev::RefitAddArgs a{};
+    tuning::PoisonArgs(&a);  // (every field set below)
+    a.leaf = column;
+    a.wide = wide ? 1 : 0;
+    a.num_leaves = num_leaves;
+    a.n = n;
+    a.values = d_values;
+    a.score = d_score;
+    dev::RefitAddLeafValues(a, nullptr);
+    OPCHECK(hipGetLastError());
+    OPCHECK(hipDeviceSynchronize());
   });
 }
 

@@ -693,6 +693,57 @@ struct RenewArgs {
 size_t RenewScratchBytes(int64_t n, int leaves);
 void RenewLeafOutputs(RenewArgs r, int64_t n, hipStream_t s);
 
+// ---- refit of an existing forest's leaf values (src/device/refit_kernels.hip): the leaf matrix
+// (the C API's row-major int32 [rows][trees]) is staged tree-major, then every tree takes one
+// pass for its per-leaf (sum g, sum h, count) and one for the score update -- no bins, no walk.
+// The fixed-point rule of the sums is in refit_quant.h.
+constexpr int kRefitThreads = 256;
+constexpr int kRefitUnroll = 4;   // rows in flight per thread of the leaf-sum pass
+constexpr int kRefitTile = 32;    // the staging transpose works on kRefitTile x kRefitTile tiles
+// Leaf sums: the three per-workgroup tables (sum g, sum h, count; 8 bytes an entry) are kept in
+// LDS up to this many leaves: 3 * 8 B * 2048 = 48 KiB, which a launch gets without opting in to
+// more than 64 KiB and which leaves room for three workgroups in a CU's 160 KiB.  Trees with more
+// leaves add straight to the global table (few rows share a leaf there: little contention)
+constexpr int kRefitLdsLeaves = 2048;
+// Score update: the tree's leaf values (8 bytes each) are staged in LDS up to 48 KiB
+constexpr int kRefitValueLdsLeaves = 6144;
+struct RefitStageArgs {
+  const int32_t* src{};         // [rows][src_stride]: the window's columns of rows [row0, row0 + rows)
+  int64_t src_stride{};
+  int64_t rows{};
+  int64_t row0{};
+  int64_t num_rows{};           // rows of the staged matrix (its column stride)
+  int32_t cols{};               // trees of the window
+  int32_t wide{};               // staged as int32 (else uint16: every tree has at most 65536 leaves)
+  const int32_t* num_leaves{};  // [cols]
+  void* out{};                  // [cols][num_rows]
+  uint32_t* bad{};              // [0] entries outside [0, num_leaves), [1] the first such column (from 0xffffffff)
+};
+// validates while it transposes; an offending entry is staged as leaf 0 and counted in bad[0]
+void RefitStage(const RefitStageArgs& a, hipStream_t s);
+struct RefitSumArgs {
+  const void* leaf{};   // [n] staged column (ids below num_leaves: RefitStage checked them)
+  int32_t wide{};
+  int32_t num_leaves{};
+  int64_t n{};
+  const float* grad{};
+  const float* hess{};
+  uint32_t* absmax{};   // [2] scratch: bits of max |g|, max |h|
+  long long* table{};   // [3 * num_leaves + 2]: sum g, sum h (fixed point), count, then the two scale exponents
+};
+void RefitLeafSums(const RefitSumArgs& a, hipStream_t s);
+struct RefitAddArgs {
+  const void* leaf{};
+  int32_t wide{};
+  int32_t num_leaves{};
+  int64_t n{};
+  const double* values{};  // [num_leaves]
+  double* score{};         // [n], updated in place
+};
+void RefitAddLeafValues(const RefitAddArgs& a, hipStream_t s);
+// workgroups of the leaf-sum pass over n rows (each thread strides by grid * kRefitThreads)
+int RefitSumGrid(int64_t n);
+
 int GradientBlocks(int64_t n);
 // absmax = (max |g|, max h, rows_cap, 0) (and root = (sum g, sum h, n) if root_parts) from
 // per-workgroup partials

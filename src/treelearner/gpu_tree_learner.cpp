@@ -94,6 +94,7 @@ void GPUTreeLearner::FreeBuffers() {
 
 void GPUTreeLearner::FreeAll() {
   FreeBuffers();
+  RefitRelease();
   if (rec_event_ != nullptr) (void)hipEventDestroy(rec_event_);
   rec_event_ = nullptr;
   if (stream_) (void)hipStreamDestroy(stream_);

@@ -92,6 +92,12 @@ class GPUTreeLearner : public SerialTreeLearner, public DeviceTreeLearner {
   std::string DebugCheckSplits(const Tree* tree) override;  // gpu_self_check.cpp
   bool RenewTreeOutputOnDevice(Tree* tree, const ObjectiveFunction* obj, int tree_id) override;
   TreeStats LastTreeStats() const override { return last_stats_; }
+  // refit from the leaf matrix (gpu_learner_refit.cpp); one process only
+  bool RefitStageWindow(const int32_t* leaf, int64_t nrow, int ncol, int col0, const int* num_leaves,
+                        int trees_per_iteration, int* cols_staged) override;
+  bool RefitLeafSums(int col, int tree_id, int num_leaves, double* sum_g, double* sum_h, data_size_t* count,
+                     int* scale_exp) override;
+  bool RefitAddLeafValues(int col, int tree_id, const double* values, int num_leaves) override;
 
   bool device_mode() const { return device_mode_; }
 
@@ -447,6 +453,24 @@ class GPUTreeLearner : public SerialTreeLearner, public DeviceTreeLearner {
     std::unordered_map<const void*, QueryInputs> queries;
     std::set<int> logged_kinds;  // metric kinds evaluated here so far (debug log)
   };
+  // refit: the staged window of the leaf matrix (columns [col0, col0 + cols), tree-major) and
+  // the per-tree scratch; own allocations, released when the refit ends
+  struct RefitState {
+    void* staged = nullptr;
+    int32_t* chunk = nullptr;       // a chunk of rows of the window's columns, row-major
+    int32_t* num_leaves = nullptr;  // [cols]
+    uint32_t* flags = nullptr;      // [0..1] RefitStageArgs::bad, [2..3] RefitSumArgs::absmax
+    long long* table = nullptr;     // RefitSumArgs::table
+    double* values = nullptr;       // a tree's leaf values
+    int table_leaves = 0;           // leaves table / values are sized for
+    int64_t nrow = 0;
+    int col0 = 0, cols = 0;
+    bool wide = false;
+    std::vector<long long> host_table;
+  };
+  RefitState refit_;
+  void RefitRelease();
+  const void* RefitColumn(int col) const;
   std::vector<ValidSet> valid_;
   int train_eval_slot_ = -1;  // valid_ entry over the training scores (d_score_; no bins)
   std::vector<void*> valid_allocs_;

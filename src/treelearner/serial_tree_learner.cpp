@@ -694,11 +694,37 @@ void SerialTreeLearner::RenewTreeOutput(Tree* tree, const ObjectiveFunction* obj
   }
 }
 
-Tree* SerialTreeLearner::FitByExistingTree(const Tree* old_tree, const score_t* g, const score_t* h) const {
+// The refitted copy of old_tree from per-leaf sums (reference SerialTreeLearner::FitByExistingTree):
+// the leaf output of (sum_g, sum_h) under lambda_l1 / lambda_l2 / max_delta_step / path_smooth,
+// times the tree's shrinkage, blended with the old value by refit_decay_rate.  sum_h carries the
+// reference's kEpsilon (its sums start there).  One formula for the CPU learner and the device
+// refit (GBDT::RefitTree).
+Tree* RefitLeafOutputs(const Tree* old_tree, const Config& config, const double* sum_g, const double* sum_h,
+                       const data_size_t* count) {
   std::unique_ptr<Tree> tree(new Tree(*old_tree));
-  const bool smooth = config_->path_smooth > kEpsilon;
-#pragma omp parallel for schedule(static)
+  const bool smooth = config.path_smooth > kEpsilon;
   for (int i = 0; i < tree->num_leaves(); ++i) {
+    double out;
+    if (smooth && i > 0) {
+      out = LeafOutputRaw(sum_g[i], sum_h[i], config.lambda_l1, config.lambda_l2, config.max_delta_step,
+                          config.path_smooth, count[i], tree->leaf_parent(i), 1, 1, 1);
+    } else {
+      out = LeafOutputRaw(sum_g[i], sum_h[i], config.lambda_l1, config.lambda_l2, config.max_delta_step,
+                          config.path_smooth, count[i], 0, 1, 1, 0);
+    }
+    const double old = tree->LeafOutput(i);
+    const double nw = out * tree->shrinkage();
+    tree->SetLeafOutput(i, config.refit_decay_rate * old + (1.0 - config.refit_decay_rate) * nw);
+  }
+  return tree.release();
+}
+
+Tree* SerialTreeLearner::FitByExistingTree(const Tree* old_tree, const score_t* g, const score_t* h) const {
+  const int nl = old_tree->num_leaves();
+  std::vector<double> sum_g(nl), sum_h(nl);
+  std::vector<data_size_t> count(nl);
+#pragma omp parallel for schedule(static)
+  for (int i = 0; i < nl; ++i) {
     data_size_t cnt;
     const data_size_t* idx = LeafIndices(i, &cnt);
     double sg = 0, sh = kEpsilon;
@@ -706,19 +732,11 @@ Tree* SerialTreeLearner::FitByExistingTree(const Tree* old_tree, const score_t* 
       sg += g[idx[j]];
       sh += h[idx[j]];
     }
-    double out;
-    if (smooth && i > 0) {
-      out = LeafOutputRaw(sg, sh, config_->lambda_l1, config_->lambda_l2, config_->max_delta_step,
-                          config_->path_smooth, cnt, tree->leaf_parent(i), 1, 1, 1);
-    } else {
-      out = LeafOutputRaw(sg, sh, config_->lambda_l1, config_->lambda_l2, config_->max_delta_step,
-                          config_->path_smooth, cnt, 0, 1, 1, 0);
-    }
-    const double old = tree->LeafOutput(i);
-    const double nw = out * tree->shrinkage();
-    tree->SetLeafOutput(i, config_->refit_decay_rate * old + (1.0 - config_->refit_decay_rate) * nw);
+    sum_g[i] = sg;
+    sum_h[i] = sh;
+    count[i] = cnt;
   }
-  return tree.release();
+  return RefitLeafOutputs(old_tree, *config_, sum_g.data(), sum_h.data(), count.data());
 }
 
 Tree* SerialTreeLearner::FitByExistingTree(const Tree* old_tree, const std::vector<int>& leaf_pred,
