@@ -202,7 +202,7 @@ struct SplitRecord {
   DeviceSplit split;
 };
 
-// ---- round growth (speculative multi-leaf expansion, round_kernels.hip)
+// ---- round growth (speculative multi-leaf expansion, round_common.h)
 // Leaf-wise growth applies one split at a time, but expanding a leaf -- partitioning its rows
 // by its best split, histogramming and scanning both children -- depends on that leaf's rows
 // only.  A round expands up to KArgs::round_k leaves at once (the current leaves of highest

@@ -2,6 +2,8 @@
 // and the fused split kernel (partition_kernels.hip).
 #pragma once
 
+#include <type_traits>
+
 #include "device_common.h"
 
 namespace lgbm_amd {
@@ -19,6 +21,47 @@ struct TileCtx {
 // row-sparse storage (KArgs::sp_ptr) takes the GPW slot of the kernels' templates
 constexpr int kSparseGPW = 1;
 constexpr int kSparsePer = kSparsePerThread;  // (KArgs::sp_team threads per row)
+
+// The bin layouts every histogram kernel is instantiated for: GPW (row-sparse, 4-bit, 1-byte,
+// 2-byte or mixed groups, see below) x UNITS (1 or 2 words per bin).  ForEachBinLayout calls
+// f(gpw, units) with std::integral_constant arguments for each of them -- the kernels'
+// allow-lists; DispatchBinLayout calls it for the layout of `a` -- their launches.  A launch
+// therefore cannot select an instantiation its allow-list misses.
+template <int V>
+using IntC = std::integral_constant<int, V>;
+// dynamic LDS above 64 KiB must be enabled per kernel (up to the CU's 160 KiB), outside any
+// graph capture
+template <typename K>
+void AllowLds(K kernel, int bytes) {
+  if (bytes > 65536 && hipFuncSetAttribute(reinterpret_cast<const void*>(kernel),
+                                           hipFuncAttributeMaxDynamicSharedMemorySize, bytes) != hipSuccess) {
+    (void)hipGetLastError();  // not fatal: launches above 64 KiB then fail loudly
+  }
+}
+template <typename F>
+void ForEachBinLayout(F&& f) {
+  auto both = [&](auto gpw) {
+    f(gpw, IntC<1>{});
+    f(gpw, IntC<2>{});
+  };
+  both(IntC<kSparseGPW>{});
+  both(IntC<8>{});
+  both(IntC<4>{});
+  both(IntC<2>{});
+  both(IntC<0>{});
+}
+template <typename F>
+void DispatchBinLayout(const KArgs& a, F&& f) {
+  auto units = [&](auto gpw) {
+    if (a.hist_units == 1) f(gpw, IntC<1>{});
+    else f(gpw, IntC<2>{});
+  };
+  if (a.sp_ptr != nullptr) units(IntC<kSparseGPW>{});
+  else if (a.nibbles) units(IntC<8>{});
+  else if (a.bin_bytes == 1) units(IntC<4>{});
+  else if (a.bin_bytes == 2) units(IntC<2>{});
+  else units(IntC<0>{});
+}
 
 // GPW: groups per word (8: 4-bit layout, 4: 8-bit layout, 2: 16-bit layout, 0: mixed layout,
 // one more round trip for the word table) or kSparseGPW; otherwise every load is independent

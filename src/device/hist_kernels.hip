@@ -145,34 +145,14 @@ static int MaxDynLds() {
   return v;
 }
 
-template <typename K>
-static void AllowLds(K kernel) {
-  const int mx = MaxDynLds();
-  if (mx > 65536 && hipFuncSetAttribute(reinterpret_cast<const void*>(kernel),
-                                        hipFuncAttributeMaxDynamicSharedMemorySize, mx) != hipSuccess) {
-    (void)hipGetLastError();  // not fatal: launches above 64 KiB then fail loudly
-  }
-}
-
 template <int MODE>
 static void LaunchHist(const KArgs& a, hipStream_t s) {
   const size_t lds_bytes = sizeof(unsigned long long) * a.hist_units * static_cast<size_t>(a.tile_bins);
 
   const dim3 grid(a.root_grid, a.hist_tiles);
-  if (a.sp_ptr != nullptr) {
-    if (a.hist_units == 1) hipLaunchKernelGGL((k_hist<MODE, kSparseGPW, 1>), grid, dim3(kHistThreads), lds_bytes, s, a);
-    else hipLaunchKernelGGL((k_hist<MODE, kSparseGPW, 2>), grid, dim3(kHistThreads), lds_bytes, s, a);
-  } else if (a.hist_units == 1) {
-    if (a.nibbles) hipLaunchKernelGGL((k_hist<MODE, 8, 1>), grid, dim3(kHistThreads), lds_bytes, s, a);
-    else if (a.bin_bytes == 1) hipLaunchKernelGGL((k_hist<MODE, 4, 1>), grid, dim3(kHistThreads), lds_bytes, s, a);
-    else if (a.bin_bytes == 2) hipLaunchKernelGGL((k_hist<MODE, 2, 1>), grid, dim3(kHistThreads), lds_bytes, s, a);
-    else hipLaunchKernelGGL((k_hist<MODE, 0, 1>), grid, dim3(kHistThreads), lds_bytes, s, a);
-  } else {
-    if (a.nibbles) hipLaunchKernelGGL((k_hist<MODE, 8, 2>), grid, dim3(kHistThreads), lds_bytes, s, a);
-    else if (a.bin_bytes == 1) hipLaunchKernelGGL((k_hist<MODE, 4, 2>), grid, dim3(kHistThreads), lds_bytes, s, a);
-    else if (a.bin_bytes == 2) hipLaunchKernelGGL((k_hist<MODE, 2, 2>), grid, dim3(kHistThreads), lds_bytes, s, a);
-    else hipLaunchKernelGGL((k_hist<MODE, 0, 2>), grid, dim3(kHistThreads), lds_bytes, s, a);
-  }
+  DispatchBinLayout(a, [&](auto gpw, auto units) {
+    hipLaunchKernelGGL((k_hist<MODE, decltype(gpw)::value, decltype(units)::value>), grid, dim3(kHistThreads), lds_bytes, s, a);
+  });
   LaunchReduce<MODE>(a, s);
 }
 
@@ -195,31 +175,15 @@ template void LaunchReduce<1>(const KArgs&, hipStream_t);
 void PrepareSplitKernels(int max_lds);
 void PrepareRoundKernels(int max_lds);
 
-// dynamic LDS above 64 KiB must be enabled per kernel (outside any graph capture)
 void PrepareKernels() {
-  AllowLds(k_hist<0, 8, 1>);
-  AllowLds(k_hist<0, 8, 2>);
-  AllowLds(k_hist<2, 8, 1>);
-  AllowLds(k_hist<2, 8, 2>);
-  AllowLds(k_hist<0, 4, 1>);
-  AllowLds(k_hist<0, 2, 1>);
-  AllowLds(k_hist<0, 4, 2>);
-  AllowLds(k_hist<0, 2, 2>);
-  AllowLds(k_hist<2, 4, 1>);
-  AllowLds(k_hist<2, 2, 1>);
-  AllowLds(k_hist<2, 4, 2>);
-  AllowLds(k_hist<2, 2, 2>);
-  AllowLds(k_hist<0, 0, 1>);
-  AllowLds(k_hist<0, 0, 2>);
-  AllowLds(k_hist<2, 0, 1>);
-  AllowLds(k_hist<2, 0, 2>);
-  AllowLds(k_hist<0, kSparseGPW, 1>);
-  AllowLds(k_hist<0, kSparseGPW, 2>);
-  AllowLds(k_hist<2, kSparseGPW, 1>);
-  AllowLds(k_hist<2, kSparseGPW, 2>);
-  PrepareSplitKernels(MaxDynLds());
-  PrepareRoundKernels(MaxDynLds());
-  PrepareRankKernels(MaxDynLds());
+  const int mx = MaxDynLds();
+  ForEachBinLayout([mx](auto gpw, auto units) {
+    AllowLds(k_hist<0, decltype(gpw)::value, decltype(units)::value>, mx);
+    AllowLds(k_hist<2, decltype(gpw)::value, decltype(units)::value>, mx);
+  });
+  PrepareSplitKernels(mx);
+  PrepareRoundKernels(mx);
+  PrepareRankKernels(mx);
 }
 
 void HistRoot(const KArgs& a, hipStream_t s) { LaunchHist<0>(a, s); }

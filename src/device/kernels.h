@@ -192,7 +192,7 @@ struct KArgs {
   int32_t vote_rank{};
   int32_t* vote_list{};
   long long* vote_hist{};
-  // round growth (round_kernels.hip; null rd: one split per step): up to round_k nodes are
+  // round growth (round_common.h; null rd: one split per step): up to round_k nodes are
   // expanded per round.  Their children's per-feature results go to feat_best rows 2j + lr,
   // each child node's best split to cbest[node] (category sets in cbest_cat); child_cnt holds
   // each child's split-scan arrival counters ([2 * kMaxRoundExp][kFindSub], kFindSubStride

@@ -273,34 +273,14 @@ static size_t SplitLds(const KArgs& a) {
   return sizeof(unsigned long long) * a.hist_units * static_cast<size_t>(a.tile_bins) + sizeof(int) * kSplitSub;
 }
 
-// dynamic LDS above 64 KiB must be enabled per kernel (up to the CU's 160 KiB)
-template <typename K>
-static void AllowLds(K kernel, int bytes) {
-  if (bytes > 65536 && hipFuncSetAttribute(reinterpret_cast<const void*>(kernel),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, bytes) != hipSuccess) {
-    (void)hipGetLastError();  // not fatal: launches above 64 KiB then fail loudly
-  }
-}
-
 template <int GR>
 static void LaunchSplit(const KArgs& a, hipStream_t s) {
   const dim3 grid(a.split_grid, a.hist_tiles);
   const size_t lds = SplitLds(a);
 
-  if (a.sp_ptr != nullptr) {
-    if (a.hist_units == 1) hipLaunchKernelGGL((k_split<kSparseGPW, 1, true, GR>), grid, dim3(kPartThreads), lds, s, a);
-    else hipLaunchKernelGGL((k_split<kSparseGPW, 2, true, GR>), grid, dim3(kPartThreads), lds, s, a);
-  } else if (a.hist_units == 1) {
-    if (a.nibbles) hipLaunchKernelGGL((k_split<8, 1, true, GR>), grid, dim3(kPartThreads), lds, s, a);
-    else if (a.bin_bytes == 1) hipLaunchKernelGGL((k_split<4, 1, true, GR>), grid, dim3(kPartThreads), lds, s, a);
-    else if (a.bin_bytes == 2) hipLaunchKernelGGL((k_split<2, 1, true, GR>), grid, dim3(kPartThreads), lds, s, a);
-    else hipLaunchKernelGGL((k_split<0, 1, true, GR>), grid, dim3(kPartThreads), lds, s, a);
-  } else {
-    if (a.nibbles) hipLaunchKernelGGL((k_split<8, 2, true, GR>), grid, dim3(kPartThreads), lds, s, a);
-    else if (a.bin_bytes == 1) hipLaunchKernelGGL((k_split<4, 2, true, GR>), grid, dim3(kPartThreads), lds, s, a);
-    else if (a.bin_bytes == 2) hipLaunchKernelGGL((k_split<2, 2, true, GR>), grid, dim3(kPartThreads), lds, s, a);
-    else hipLaunchKernelGGL((k_split<0, 2, true, GR>), grid, dim3(kPartThreads), lds, s, a);
-  }
+  DispatchBinLayout(a, [&](auto gpw, auto units) {
+    hipLaunchKernelGGL((k_split<decltype(gpw)::value, decltype(units)::value, true, GR>), grid, dim3(kPartThreads), lds, s, a);
+  });
 }
 
 void SplitStep(const KArgs& a, hipStream_t s, bool reduce) {
@@ -309,23 +289,12 @@ void SplitStep(const KArgs& a, hipStream_t s, bool reduce) {
   if (reduce) LaunchReduce<1>(a, s);
 }
 
-template <int GR>
-static void AllowSplitLds(int mx) {
-  AllowLds(k_split<8, 1, true, GR>, mx);
-  AllowLds(k_split<8, 2, true, GR>, mx);
-  AllowLds(k_split<4, 1, true, GR>, mx);
-  AllowLds(k_split<2, 1, true, GR>, mx);
-  AllowLds(k_split<4, 2, true, GR>, mx);
-  AllowLds(k_split<2, 2, true, GR>, mx);
-  AllowLds(k_split<0, 1, true, GR>, mx);
-  AllowLds(k_split<0, 2, true, GR>, mx);
-  AllowLds(k_split<kSparseGPW, 1, true, GR>, mx);
-  AllowLds(k_split<kSparseGPW, 2, true, GR>, mx);
-}
-
 void PrepareSplitKernels(int mx) {
-  AllowSplitLds<kGatherNarrow>(mx);
-  AllowSplitLds<kGatherWide>(mx);
+  ForEachBinLayout([mx](auto gpw, auto units) {
+    constexpr int G = decltype(gpw)::value, U = decltype(units)::value;
+    AllowLds(k_split<G, U, true, kGatherNarrow>, mx);
+    AllowLds(k_split<G, U, true, kGatherWide>, mx);
+  });
 }
 
 void Partition(const KArgs& a, hipStream_t s) {

@@ -1,5 +1,5 @@
 // Split-scan primitives shared by the one-split-per-step kernels (split_kernels.hip) and the
-// round-growth kernels (round_kernels.hip): block scans / argmaxes, the numerical threshold
+// round-growth kernels (round_find.hip, round_plan.h): block scans / argmaxes, the numerical threshold
 // scan with FixHistogram (reference feature_histogram.hpp FindBestThresholdSequentially,
 // FuncForNumricalL3, FixHistogram) and the categorical scan (FindBestThresholdCategoricalInner).
 #pragma once

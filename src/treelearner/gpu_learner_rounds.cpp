@@ -1,5 +1,5 @@
 // MI355X tree learner: round growth orchestration -- pools, the round sequence and its
-// collectives, the growth-mode choice and the host loop over round segments (round_kernels.hip).
+// collectives, the growth-mode choice and the host loop over round segments (src/device/round_common.h).
 #include <atomic>
 #include <chrono>
 #include <thread>

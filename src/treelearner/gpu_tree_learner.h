@@ -162,7 +162,7 @@ class GPUTreeLearner : public SerialTreeLearner, public DeviceTreeLearner {
   template <typename T>
   T* Alloc(size_t n);
 
-  // round growth (speculative multi-leaf expansion, src/device/round_kernels.hip): up to
+  // round growth (speculative multi-leaf expansion, src/device/round_common.h): up to
   // round_k_ leaves expanded per round; whether this tree may (plan_.growth)
   bool RoundGrowth() const;
   bool CegbRounds() const;  // Growth::kRoundsOnceSampleUsed, resolved for this tree

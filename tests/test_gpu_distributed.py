@@ -214,7 +214,7 @@ def test_device_distributed_with_efb_bundles(learner, gpu_available):
                                                   ("data", 3, 8, "cegb"), ("feature", 3, 8, "cegb")])
 def test_distributed_round_growth_equals_one_split_per_step(learner, world, k, mode, gpu_available, monkeypatch,
                                                             tmp_path):
-    """Distributed round growth (round_kernels.hip: up to k leaves expanded per round, the
+    """Distributed round growth (round_split.hip / round_find.hip: up to k leaves expanded per round, the
     histograms reduce-scattered and the per-feature records gathered once per round instead of
     once per split; voting: one proposal allgather and one elected-histogram all-reduce per
     round for all of the round's children) grows the same trees as one split per step

@@ -1,4 +1,4 @@
-"""Round growth (speculative multi-leaf expansion, src/device/round_kernels.hip) grows the
+"""Round growth (speculative multi-leaf expansion, src/device/round_common.h) grows the
 trees of one-split-per-step growth, bit for bit.
 
 Each round expands the current leaves of highest gain at once (partition + children's
@@ -137,6 +137,33 @@ def test_round_kernel_variants(fused, monkeypatch, tmp_path, gpu_available):
     base, _ = _model(monkeypatch, tmp_path, 1, X, y, params, rounds=4, tag="v" + fused)
     monkeypatch.setenv("LGBM_AMD_ROUND_FUSED", fused)
     spec, _ = _model(monkeypatch, tmp_path, 8, X, y, params, rounds=4, tag="v" + fused)
+    assert base == spec
+
+
+PLANNER_PATHS = {
+    # register replay + PredictRegs, the plan inside the scan kernel
+    "walk_regs": ({"LGBM_AMD_ROUND_PREDICT": "0"}, {"objective": "binary", "num_leaves": 31}),
+    # LDS replay + LDS step walk, k_round_plan
+    "walk_lds": ({"LGBM_AMD_ROUND_PREDICT": "0"}, {"objective": "binary", "num_leaves": 127, "min_data_in_leaf": 5}),
+    # k_round_plan<false> with the register replay and the default prediction
+    "plan_kernel": ({"LGBM_AMD_PLAN_IN_FIND": "0"}, {"objective": "binary", "num_leaves": 31}),
+    # the extra_trees instantiation of the plan with the step walk
+    "walk_xt": ({"LGBM_AMD_ROUND_PREDICT": "0"}, {"objective": "binary", "num_leaves": 31, "extra_trees": True}),
+}
+
+
+@pytest.mark.parametrize("path", list(PLANNER_PATHS))
+def test_round_planner_paths(path, monkeypatch, tmp_path, gpu_available):
+    """The planner's selectable paths (src/device/round_plan.h): the step-walk prediction in its
+    register and LDS forms, the plan in a kernel of its own on a small tree, and the extra_trees
+    instantiation with the step walk."""
+    env, params = PLANNER_PATHS[path]
+    X, y = _data()
+    base, _ = _model(monkeypatch, tmp_path, 1, X, y, params, rounds=4, tag=path)
+    for k, v in env.items():
+        monkeypatch.setenv(k, v)
+    spec, rows = _model(monkeypatch, tmp_path, 8, X, y, params, rounds=4, tag=path)
+    assert all(r > 0 for row in rows for r in row["rounds"])
     assert base == spec
 
 
