@@ -182,7 +182,9 @@ bool GBDT::PredictDenseOnDevice(const void* data, bool is_double, int64_t nrow, 
   int ndev = 0;
   if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return false;
   if (num_tree_per_iteration_ > dev::kMaxPredClasses || nrow <= 0) return false;
-  if (kind != DevicePredictKind::Normal && kind != DevicePredictKind::Raw && ncol <= max_feature_idx_) return false;
+  // (a matrix narrower than the model, let through by predict_disable_shape_check: the kernels index
+  // a row by the model's features, and the host predictor reads the absent columns as 0)
+  if (ncol <= max_feature_idx_) return false;
   const int ntpi = num_tree_per_iteration_;
   // (the forest is rebuilt per call: trees may have been edited in place)
   const std::vector<const Tree*> trees = PredictWindowTrees(start_iteration, num_iteration);

@@ -1,9 +1,9 @@
-// The decision of one flattened-forest node on a raw feature value, shared by the SHAP / leaf
+// The decision of one flattened-forest node on a raw feature value: the device's one statement
+// of the rule, shared by the score kernel (src/device/predict_kernels.hip), the SHAP / leaf
 // kernels (src/device/shap_kernels.hip) and the host evaluator of the path tables
-// (src/boosting/shap_paths.cpp).  Same semantics as the walk of k_predict_forest
-// (src/device/predict_kernels.hip): reference Tree::NumericalDecision / CategoricalDecision with
-// the dense C API rows' |v| <= kZeroThreshold read as 0.  One value is decided as the host
-// decides it and not as that kernel does: a NaN at a categorical split (see below).
+// (src/boosting/shap_paths.cpp).  Same semantics as the host predictor: reference
+// Tree::NumericalDecision / CategoricalDecision with the dense C API rows' |v| <= kZeroThreshold
+// read as 0.  tests/helpers/forest_ref.py states the rule apart from the code.
 #pragma once
 
 #include <cmath>

@@ -5,16 +5,15 @@
 // One thread per row walks every tree in model order, accumulating the raw score of each
 // class in registers in the same order as the host predictor (bit-identical sums).  The
 // flattened forest (a few hundred KB for 500 x 63-leaf trees) stays L2-resident and every
-// wave reads the same node at the same time; dense rows follow the C API's convention of
-// treating |v| <= kZeroThreshold as 0.
+// wave reads the same node at the same time.  A node is decided by ForestGoesLeft
+// (forest_decision.h), the device's one statement of the rule.
 #include "device_common.h"
+#include "forest_decision.h"
 
 namespace lgbm_amd {
 namespace dev {
 
 namespace {
-
-constexpr double kPredZero = 1e-35f;  // kZeroThreshold
 
 template <typename T, bool ROW_MAJOR>
 __global__ __launch_bounds__(256) void k_predict_forest(ForestArgs f) {
@@ -32,36 +31,9 @@ __global__ __launch_bounds__(256) void k_predict_forest(ForestArgs f) {
       while (node >= 0) {
         const int gi = n0 + node;
         const int feat = f.feature[gi];
-        double v = ROW_MAJOR ? static_cast<double>(x[row * f.num_cols + feat])
-                             : static_cast<double>(x[static_cast<int64_t>(feat) * f.num_rows + row]);
-        if (fabs(v) <= kPredZero) v = 0.0;
-        const int8_t dt = f.dtype[gi];
-        const int mt = (dt >> 2) & 3;
-        bool left;
-        if (dt & 1) {  // categorical
-          int iv = static_cast<int>(v);
-          if (iv < 0) {
-            left = false;
-          } else if (v != v && mt == 2) {
-            left = false;
-          } else {
-            if (v != v) iv = 0;
-            const int32_t* bound = f.cat_bound + f.cat_bound_off[t];
-            const uint32_t* bits = f.cat_bits + f.cat_bits_off[t];
-            const int ci = static_cast<int>(f.threshold[gi]);
-            const int lo = bound[ci], nw = bound[ci + 1] - lo;
-            const int w = iv >> 5;
-            left = w < nw && ((bits[lo + w] >> (iv & 31)) & 1u);
-          }
-        } else {
-          if (v != v && mt != 2) v = 0.0;
-          if ((mt == 1 && fabs(v) <= kPredZero) || (mt == 2 && v != v)) {
-            left = (dt & 2) != 0;
-          } else {
-            left = v <= f.threshold[gi];
-          }
-        }
-        node = left ? f.left[gi] : f.right[gi];
+        const double v = ROW_MAJOR ? static_cast<double>(x[row * f.num_cols + feat])
+                                   : static_cast<double>(x[static_cast<int64_t>(feat) * f.num_rows + row]);
+        node = ForestGoesLeft(f, t, gi, v) ? f.left[gi] : f.right[gi];
       }
       leaf = ~node;
     }

@@ -229,11 +229,13 @@ def test_booster_trained_on_the_device(monkeypatch):
 
 def test_nan_in_a_categorical_column_goes_where_the_host_sends_it(monkeypatch):
     """the host predictor sends a NaN right at every categorical split (its int cast is negative),
-    whatever the split's missing type; leaf indices and contributions follow it"""
+    whatever the split's missing type; raw scores, leaf indices and contributions follow it"""
     c = cc.case("categorical_zero_missing")
     X = c.X.copy()
     X[::3, 1] = np.nan
     X[1::4, 3] = np.nan
     assert np.array_equal(_device(c.booster, X, pred_leaf=True), _host(monkeypatch, c.booster, X, pred_leaf=True))
+    raw_d = _device(c.booster, X, raw_score=True)
+    assert np.array_equal(raw_d, _host(monkeypatch, c.booster, X, raw_score=True))
     cc.check_contrib(_device(c.booster, X, pred_contrib=True), _host(monkeypatch, c.booster, X, pred_contrib=True),
-                     _host(monkeypatch, c.booster, X, raw_score=True), c, "NaN categories")
+                     raw_d, c, "NaN categories")
