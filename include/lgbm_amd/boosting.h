@@ -144,6 +144,27 @@ class GBDT {
   void CsrToSlotsOnHost(const void* indptr, bool indptr_is_64, const int32_t* indices, const void* data,
                         bool is_double, int64_t nindptr, int64_t nelem, int start_iteration, int num_iteration,
                         int32_t* num_used, int32_t* used, void* matrix);
+  // the same predictions of the num_row rows of a host CSC matrix (col_ptr int32 / int64, ncol_ptr
+  // = columns + 1 entries; indices: the row of each entry): only the stored entries of the columns
+  // the window's trees split on go to the device, where they stay for the call, and each chunk of
+  // rows is scattered from them into the compact matrix.  Absent entries are 0, columns the model
+  // does not have are ignored, an entry whose row is outside the matrix is dropped, and of several
+  // stored entries on one cell the last stored one wins.  false as for the CSR matrix, or when the
+  // pointer does not ascend within nelem or the entries do not fit the free memory
+  bool PredictCSCOnDevice(const void* col_ptr, bool col_ptr_is_64, const int32_t* indices, const void* data,
+                          bool is_double, int64_t ncol_ptr, int64_t nelem, int64_t num_row, int start_iteration,
+                          int num_iteration, DevicePredictKind kind, double* out);
+  // ... and of CSC arrays in device memory (the pointer of all ncol columns) into out_len doubles
+  // of device memory; what is not applicable is an error
+  void PredictCSCDeviceBuffers(const void* d_col_ptr, bool col_ptr_is_64, const int32_t* d_indices,
+                               const void* d_data, bool is_double, int64_t ncol, int64_t nelem, int64_t nrow,
+                               int start_iteration, int num_iteration, DevicePredictKind kind, double* d_out,
+                               int64_t out_len);
+  // the compact matrix of the rows [row0, row0 + rows) of a host CSC matrix evaluated on the host
+  // (tests; needs no device), as CsrToSlotsOnHost gives it for CSR rows
+  void CscToSlotsOnHost(const void* col_ptr, bool col_ptr_is_64, const int32_t* indices, const void* data,
+                        bool is_double, int64_t ncol_ptr, int64_t nelem, int64_t row0, int64_t rows,
+                        int start_iteration, int num_iteration, int32_t* num_used, int32_t* used, void* matrix);
   // predictions this process has computed on the device (tests: which path a call took)
   static int64_t DevicePredictions();
   // contributions of row-major float64 host rows from the path tables the device kernel reads,

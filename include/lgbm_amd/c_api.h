@@ -266,6 +266,20 @@ LIGHTGBM_C_EXPORT int LGBM_AMD_CsrToSlots(BoosterHandle handle, const void* indp
                                           const int32_t* indices, const void* data, int data_type, int64_t nindptr,
                                           int64_t nelem, int start_iteration, int num_iteration,
                                           int32_t* out_num_used, int32_t* out_used, void* out_matrix);
+// the same for the rows [row0, row0 + rows) of a CSC matrix of num_row rows (col_ptr: ncol_ptr =
+// columns + 1 int32 / int64 entries; indices: the row of each of the nelem stored entries), with the
+// rule of src/device/csc_slots.h: out_matrix is row-major [rows][*out_num_used].  An entry whose
+// row is outside the window is dropped, col_ptr is clamped to nelem, features past the matrix's
+// columns read 0, and of several stored entries on one cell the last stored one wins
+LIGHTGBM_C_EXPORT int LGBM_AMD_CscToSlots(BoosterHandle handle, const void* col_ptr, int col_ptr_type,
+                                          const int32_t* indices, const void* data, int data_type, int64_t ncol_ptr,
+                                          int64_t nelem, int64_t num_row, int64_t row0, int64_t rows,
+                                          int start_iteration, int num_iteration, int32_t* out_num_used,
+                                          int32_t* out_used, void* out_matrix);
+// the launch shape of the CSC scatter (src/device/csc_kernels.hip; tests place columns on its
+// boundaries): out[0] the stored entries of a segment, the share of a column that one wave takes,
+// out[1] the threads of a workgroup, out[2] the entries of a batch of the single-wave path
+LIGHTGBM_C_EXPORT int LGBM_AMD_CscLaunchInfo(int64_t* out);
 // the per-leaf sums of a device refit, evaluated on the host with the kernel's fixed-point rule
 // (src/device/refit_quant.h; no GPU needed): leaf[n] in [0, num_leaves) (anything else is an
 // error), grad / hess[n]; out_sums[2 * num_leaves] receives sum g then sum h per leaf

@@ -34,7 +34,7 @@ from .._native import LightGBMError, call as _native_call, params_str as param_d
 from ..basic import _load_lib
 
 __all__ = ["gradients", "metric", "sample_rows", "forest_predict", "leaf_sums", "add_leaf_values",
-           "refit_launch_info"]
+           "refit_launch_info", "csc_launch_info"]
 
 
 def _torch():
@@ -193,20 +193,28 @@ def forest_predict(booster, X, kind="raw", start_iteration=0, num_iteration=-1):
     ``X`` may also be a ``torch.sparse_csr`` GPU tensor with float32 or float64 values (int32 or
     int64 ``crow_indices``; int64 ``col_indices`` are converted to int32 on the device): absent
     entries are 0, columns the model does not have are ignored, and the rows are scattered on
-    the device into a matrix of the features the trees split on (src/device/csr_kernels.hip)."""
+    the device into a matrix of the features the trees split on (src/device/csr_kernels.hip).
+
+    A ``torch.sparse_csc`` GPU tensor is taken the same way (int32 or int64 ``ccol_indices``;
+    int64 ``row_indices`` are converted to int32 on the device): only the columns the trees split
+    on are read (src/device/csc_kernels.hip), and of several stored entries on one cell the last
+    stored one is the value."""
     torch = _torch()
     if kind not in _FOREST_KINDS:
         raise LightGBMError("kind must be one of 'raw', 'leaf', 'contrib', got %r" % (kind,))
     if not isinstance(X, torch.Tensor) or X.dim() != 2 or X.dtype not in (torch.float32, torch.float64):
         raise LightGBMError("X must be a 2-d float32 or float64 torch tensor on the GPU")
-    sparse = X.layout == torch.sparse_csr
+    sparse = X.layout in (torch.sparse_csr, torch.sparse_csc)
+    csc = X.layout == torch.sparse_csc
     if sparse:
-        crow, col, values = X.crow_indices(), X.col_indices(), X.values()
+        crow, col = (X.ccol_indices(), X.row_indices()) if csc else (X.crow_indices(), X.col_indices())
+        values = X.values()
+        names = ("ccol_indices", "row_indices") if csc else ("crow_indices", "col_indices")
         if crow.dtype not in (torch.int32, torch.int64):
-            raise LightGBMError("crow_indices must be int32 or int64")
+            raise LightGBMError("%s must be int32 or int64" % names[0])
         crow, values = crow.contiguous(), values.contiguous()
         col = col.to(torch.int32).contiguous()
-        ptrs = (_dev_ptr(crow, crow.dtype, "crow_indices"), _dev_ptr(col, torch.int32, "col_indices"),
+        ptrs = (_dev_ptr(crow, crow.dtype, names[0]), _dev_ptr(col, torch.int32, names[1]),
                 _dev_ptr(values, X.dtype, "values"))
     else:
         data = _dev_ptr(X, X.dtype, "X")
@@ -218,6 +226,14 @@ def forest_predict(booster, X, kind="raw", start_iteration=0, num_iteration=-1):
                  ctypes.c_int(start), ctypes.c_int(num), ctypes.byref(width))
     out = torch.empty((n, width.value), dtype=torch.float64, device=X.device)
     torch.cuda.synchronize(X.device)
+    if csc:
+        _check(_lib().LGBMAMD_OpForestPredictCSC(
+            booster.handle, ptrs[0], ctypes.c_int(2 if crow.dtype == torch.int32 else 3), ptrs[1], ptrs[2],
+            ctypes.c_int(0 if X.dtype == torch.float32 else 1), ctypes.c_int64(crow.numel() - 1),
+            ctypes.c_int64(values.numel()), ctypes.c_int64(n), ctypes.c_int(_FOREST_KINDS[kind]),
+            ctypes.c_int(start), ctypes.c_int(num), _dev_ptr(out, torch.float64, "out"),
+            ctypes.c_int64(out.numel())))
+        return out
     if sparse:
         _check(_lib().LGBMAMD_OpForestPredictCSR(
             booster.handle, ptrs[0], ctypes.c_int(2 if crow.dtype == torch.int32 else 3), ptrs[1], ptrs[2],
@@ -241,6 +257,16 @@ def refit_launch_info():
     out = (ctypes.c_int64 * 5)()
     _check(_lib().LGBMAMD_OpRefitLaunchInfo(out))
     return {"lds_leaves": out[0], "max_grid": out[1], "block": out[2], "unroll": out[3], "value_lds_leaves": out[4]}
+
+
+def csc_launch_info():
+    """The launch shape of the CSC scatter of :func:`forest_predict` (src/device/csc_kernels.hip):
+    ``segment_entries`` (the stored entries of a column that one wave takes: a longer column is
+    cut into that many entries per wave), ``block`` (threads of a workgroup) and ``batch`` (the
+    entries the single wave of a column with repeated or unsorted rows reads at a time)."""
+    out = (ctypes.c_int64 * 3)()
+    _native_call("LGBM_AMD_CscLaunchInfo", out)
+    return {"segment_entries": out[0], "block": out[1], "batch": out[2]}
 
 
 def leaf_sums(leaf, grad, hess, num_leaves):

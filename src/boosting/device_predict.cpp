@@ -11,6 +11,11 @@
 // the device into a compact matrix with one column per feature the window's trees split on
 // (FeatureSlots, src/device/csr_kernels.hip), and the forest is uploaded with its split features
 // rewritten to those columns, so the same kernels walk it.
+//
+// CSC matrices (LGBM_BoosterPredictForCSC) fill the same compact matrix from the other side: a
+// feature the trees split on is one column of the matrix, a contiguous run of stored entries.
+// Only those runs are uploaded, once per call; every chunk of rows is then scattered from them
+// (src/device/csc_kernels.hip).
 #include <hip/hip_runtime_api.h>
 #include <omp.h>
 
@@ -18,6 +23,7 @@
 #include <cstring>
 #include <vector>
 
+#include "../device/csc_slots.h"
 #include "../device/csr_slots.h"
 #include "../device/kernels.h"
 #include "shap_paths.h"
@@ -64,7 +70,7 @@ struct DeviceBuffers {
 class DeviceForest {
  public:
   // false: the contribution kernel cannot run this forest (the host predicts)
-  // slots: the forest walks a compact matrix of the features it splits on (CSR rows)
+  // slots: the forest walks a compact matrix of the features it splits on (CSR rows, CSC columns)
   bool Upload(const std::vector<const Tree*>& trees, int num_class, int num_features, DevicePredictKind kind,
               hipStream_t s, bool slots = false) {
     kind_ = kind;
@@ -109,6 +115,8 @@ class DeviceForest {
   }
   int NumSlots() const { return static_cast<int>(slots_.used.size()); }
   const int32_t* SlotOf() const { return slot_of_; }
+  // the sorted features of the slots
+  const std::vector<int32_t>& Used() const { return slots_.used; }
   // doubles of one row's output
   int64_t OutPerRow() const {
     if (kind_ == DevicePredictKind::Leaf) return f_.num_trees;
@@ -463,6 +471,223 @@ void GBDT::CsrToSlotsOnHost(const void* indptr, bool indptr_is_64, const int32_t
   } else {
     if (indptr_is_64) dev::EvalCsrToSlots(static_cast<const int64_t*>(indptr), 0, indices, static_cast<const float*>(data), rows, nelem, so, nf, ns, static_cast<float*>(matrix));
     else dev::EvalCsrToSlots(static_cast<const int32_t*>(indptr), 0, indices, static_cast<const float*>(data), rows, nelem, so, nf, ns, static_cast<float*>(matrix));
+  }
+}
+
+namespace {
+
+// the scatter arguments of CSC arrays on the device; `d_ascending` holds a word per slot
+dev::CscSlotsArgs CscArgs(const DeviceForest& forest, const void* d_col_ptr, bool col_ptr_is_64,
+                          const int32_t* d_slot_col, const int32_t* d_indices, const void* d_data, bool is_double,
+                          int64_t entries, uint32_t* d_ascending) {
+  dev::CscSlotsArgs c{};
+  tuning::PoisonArgs(&c);  // (every field set below, the chunk by RunCscToSlots)
+  c.col_ptr_is_64 = col_ptr_is_64 ? 1 : 0;
+  c.is_double = is_double ? 1 : 0;
+  c.num_slots = forest.NumSlots();
+  c.pad = 0;
+  c.num_entries = entries;
+  c.row0 = 0;
+  c.num_rows = 0;
+  c.col_ptr = d_col_ptr;
+  c.slot_col = d_slot_col;
+  c.indices = d_indices;
+  c.data = d_data;
+  c.ascending = d_ascending;
+  c.out = nullptr;
+  return c;
+}
+
+// the scatter of the rows [row0, row0 + rows) into d_mat (after dev::CscColumnOrder on the stream)
+void RunCscToSlots(dev::CscSlotsArgs c, int64_t row0, int64_t rows, void* d_mat, hipStream_t s) {
+  c.row0 = row0;
+  c.num_rows = rows;
+  c.out = d_mat;
+  dev::CscToSlots(c, s);
+  HIPCHECK(hipGetLastError());
+}
+
+}  // namespace
+
+bool GBDT::PredictCSCOnDevice(const void* col_ptr, bool col_ptr_is_64, const int32_t* indices, const void* data,
+                              bool is_double, int64_t ncol_ptr, int64_t nelem, int64_t num_row, int start_iteration,
+                              int num_iteration, DevicePredictKind kind, double* out) {
+  int ndev = 0;
+  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return false;
+  const int64_t ncol = ncol_ptr - 1;
+  if (num_tree_per_iteration_ > dev::kMaxPredClasses || num_row <= 0 || ncol < 0 || nelem < 0) return false;
+  // (columns are copied by their pointer entries: a matrix whose pointer does not ascend within
+  // the stored entries is left to the host)
+  if (PtrAt(col_ptr, col_ptr_is_64, 0) < 0 || PtrAt(col_ptr, col_ptr_is_64, ncol) > nelem) return false;
+  for (int64_t c = 0; c < ncol; ++c) {
+    if (PtrAt(col_ptr, col_ptr_is_64, c) > PtrAt(col_ptr, col_ptr_is_64, c + 1)) return false;
+  }
+  const int ntpi = num_tree_per_iteration_;
+  const int num_features = max_feature_idx_ + 1;
+  const std::vector<const Tree*> trees = PredictWindowTrees(start_iteration, num_iteration);
+  hipStream_t s;
+  HIPCHECK(hipStreamCreateWithFlags(&s, hipStreamNonBlocking));
+  bool ran = false;
+  {
+    DeviceForest forest;
+    if (forest.Upload(trees, ntpi, num_features, kind, s, true)) {
+      const size_t elem = is_double ? 8 : 4;
+      const int nslot = forest.NumSlots();
+      const int64_t per_out = forest.OutPerRow();
+      // the stored entries of the used columns, packed slot after slot: a pointer of nslot + 1
+      // entries over them, and the runs of adjacent used columns, each one copy
+      struct Run {
+        int64_t src, dst, len;
+      };
+      std::vector<int64_t> ptr(static_cast<size_t>(nslot) + 1, 0);
+      std::vector<int32_t> slot_col(nslot, -1);
+      std::vector<Run> runs;
+      for (int k = 0; k < nslot; ++k) {
+        const int64_t f = forest.Used()[k];
+        ptr[k + 1] = ptr[k];
+        if (f >= ncol) continue;  // (a matrix narrower than the model: the feature reads 0)
+        slot_col[k] = k;
+        const int64_t a = PtrAt(col_ptr, col_ptr_is_64, f), b = PtrAt(col_ptr, col_ptr_is_64, f + 1);
+        ptr[k + 1] = ptr[k] + (b - a);
+        if (b == a) continue;
+        if (!runs.empty() && runs.back().src + runs.back().len == a) runs.back().len += b - a;
+        else runs.push_back({a, ptr[k], b - a});
+      }
+      const int64_t entries = ptr[nslot];
+      // rows per chunk: the compact matrix, the output and the accumulator tiles within most of
+      // the free memory, next to the entries, which stay on the device for the call
+      size_t free_b = 0, total_b = 0;
+      HIPCHECK(hipMemGetInfo(&free_b, &total_b));
+      const size_t per_row = static_cast<size_t>(nslot) * elem + static_cast<size_t>(per_out) * sizeof(double);
+      const size_t budget = free_b - free_b / 5;
+      const size_t fixed = forest.ScratchBytes(num_row) + static_cast<size_t>(entries) * (sizeof(int32_t) + elem) +
+                           (static_cast<size_t>(nslot) + 1) * (sizeof(int64_t) + 2 * sizeof(int32_t));
+      const bool fits = fixed + static_cast<size_t>(dev::kShapLanes) * per_row <= budget;
+      if (fits) {
+        int64_t chunk = static_cast<int64_t>((budget - fixed) / per_row);
+        chunk = std::max<int64_t>(dev::kShapLanes, chunk / dev::kShapLanes * dev::kShapLanes);
+        const int forced = tuning::Int(tuning::Knob::PredictChunkRows, 0);
+        if (forced > 0) chunk = forced;
+        chunk = std::min(chunk, num_row);
+        DeviceBuffers b;
+        const int64_t* d_ptr = b.Upload(ptr, s);
+        const int32_t* d_slot_col = b.Upload(slot_col, s);
+        int32_t* d_indices = static_cast<int32_t*>(b.Alloc(static_cast<size_t>(entries) * sizeof(int32_t)));
+        char* d_data = static_cast<char*>(b.Alloc(static_cast<size_t>(entries) * elem));
+        uint32_t* d_ascending = static_cast<uint32_t*>(b.Alloc(static_cast<size_t>(nslot) * sizeof(uint32_t)));
+        // (every run where it lies: packing the runs on the host first, for two large copies, was
+        // measured slower at 266 runs -- profiles/r12_device_csc_predict.md)
+        for (const Run& r : runs) {
+          HIPCHECK(hipMemcpyAsync(d_indices + r.dst, indices + r.src, static_cast<size_t>(r.len) * sizeof(int32_t),
+                                  hipMemcpyHostToDevice, s));
+          HIPCHECK(hipMemcpyAsync(d_data + static_cast<size_t>(r.dst) * elem,
+                                  static_cast<const char*>(data) + static_cast<size_t>(r.src) * elem,
+                                  static_cast<size_t>(r.len) * elem, hipMemcpyHostToDevice, s));
+        }
+        const dev::CscSlotsArgs c = CscArgs(forest, d_ptr, true, d_slot_col, d_indices, d_data, is_double, entries,
+                                            d_ascending);
+        dev::CscColumnOrder(c, s);
+        HIPCHECK(hipGetLastError());
+        void* d_mat = b.Alloc(static_cast<size_t>(chunk) * nslot * elem);
+        double* d_out = static_cast<double*>(b.Alloc(static_cast<size_t>(chunk) * per_out * sizeof(double)));
+        const bool convert = kind == DevicePredictKind::Normal;
+        std::vector<double> raw_out(convert ? static_cast<size_t>(num_row) * per_out : 0);
+        double* host_out = convert ? raw_out.data() : out;
+        for (int64_t r0 = 0; r0 < num_row; r0 += chunk) {
+          const int64_t rows = std::min(chunk, num_row - r0);
+          RunCscToSlots(c, r0, rows, d_mat, s);
+          forest.Run(d_mat, is_double, false, rows, nslot, d_out, s);
+          HIPCHECK(hipMemcpyAsync(host_out + r0 * per_out, d_out, static_cast<size_t>(rows) * per_out * sizeof(double),
+                                  hipMemcpyDeviceToHost, s));
+          HIPCHECK(hipStreamSynchronize(s));
+        }
+        ran = true;
+        ++g_device_predictions;
+        if (convert) {
+#pragma omp parallel for schedule(static)
+          for (int64_t r = 0; r < num_row; ++r) {
+            double* o = out + r * ntpi;
+            std::memcpy(o, raw_out.data() + r * ntpi, sizeof(double) * ntpi);
+            if (average_output_) {
+              for (int k = 0; k < ntpi; ++k) o[k] /= num_iteration_for_pred_;
+            }
+            if (objective_ != nullptr) objective_->ConvertOutput(o, o);
+          }
+        }
+      }
+    }
+  }
+  HIPCHECK(hipStreamDestroy(s));
+  return ran;
+}
+
+void GBDT::PredictCSCDeviceBuffers(const void* d_col_ptr, bool col_ptr_is_64, const int32_t* d_indices,
+                                   const void* d_data, bool is_double, int64_t ncol, int64_t nelem, int64_t nrow,
+                                   int start_iteration, int num_iteration, DevicePredictKind kind, double* d_out,
+                                   int64_t out_len) {
+  if (kind == DevicePredictKind::Normal) Log::Fatal("device buffers are predicted as raw scores, leaf indices or contributions");
+  if (num_tree_per_iteration_ > dev::kMaxPredClasses) {
+    Log::Fatal("forest prediction on the device handles at most %d trees per iteration", dev::kMaxPredClasses);
+  }
+  if (nrow < 0 || nelem < 0 || ncol < 0) {
+    Log::Fatal("CSC device buffers: %lld rows, %lld columns, %lld entries", static_cast<long long>(nrow),
+               static_cast<long long>(ncol), static_cast<long long>(nelem));
+  }
+  const std::vector<const Tree*> trees = PredictWindowTrees(start_iteration, num_iteration);
+  DeviceForest forest;
+  if (!forest.Upload(trees, num_tree_per_iteration_, max_feature_idx_ + 1, kind, nullptr, true)) {
+    Log::Fatal("contributions on the device need paths of at most %d distinct features and data counts on every node",
+               dev::kShapMaxPathLen - 1);
+  }
+  if (out_len != nrow * forest.OutPerRow()) {
+    Log::Fatal("output holds %lld doubles, the prediction has %lld", static_cast<long long>(out_len),
+               static_cast<long long>(nrow * forest.OutPerRow()));
+  }
+  if (nrow > 0) {
+    const int nslot = forest.NumSlots();
+    // (the full pointer stays on the device: a slot names its feature's column, if the matrix has it)
+    std::vector<int32_t> slot_col(nslot, -1);
+    for (int k = 0; k < nslot; ++k) {
+      if (forest.Used()[k] < ncol) slot_col[k] = forest.Used()[k];
+    }
+    DeviceBuffers b;
+    const int32_t* d_slot_col = b.Upload(slot_col, nullptr);
+    uint32_t* d_ascending = static_cast<uint32_t*>(b.Alloc(static_cast<size_t>(nslot) * sizeof(uint32_t)));
+    void* d_mat = b.Alloc(static_cast<size_t>(nrow) * nslot * (is_double ? 8 : 4));
+    const dev::CscSlotsArgs c = CscArgs(forest, d_col_ptr, col_ptr_is_64, d_slot_col, d_indices, d_data, is_double,
+                                        nelem, d_ascending);
+    dev::CscColumnOrder(c, nullptr);
+    HIPCHECK(hipGetLastError());
+    RunCscToSlots(c, 0, nrow, d_mat, nullptr);
+    forest.Run(d_mat, is_double, false, nrow, nslot, d_out, nullptr);
+    HIPCHECK(hipStreamSynchronize(nullptr));
+  }
+  ++g_device_predictions;
+}
+
+void GBDT::CscToSlotsOnHost(const void* col_ptr, bool col_ptr_is_64, const int32_t* indices, const void* data,
+                            bool is_double, int64_t ncol_ptr, int64_t nelem, int64_t row0, int64_t rows,
+                            int start_iteration, int num_iteration, int32_t* num_used, int32_t* used, void* matrix) {
+  const std::vector<const Tree*> trees = PredictWindowTrees(start_iteration, num_iteration);
+  FlatForest flat;
+  flat.Build(trees);
+  FeatureSlots slots;
+  slots.Build(flat, max_feature_idx_ + 1);
+  const int ns = static_cast<int>(slots.used.size());
+  *num_used = ns;
+  if (used != nullptr) std::copy(slots.used.begin(), slots.used.end(), used);
+  if (matrix == nullptr || rows <= 0) return;
+  std::vector<int32_t> slot_col(ns, -1);
+  for (int k = 0; k < ns; ++k) {
+    if (slots.used[k] < ncol_ptr - 1) slot_col[k] = slots.used[k];
+  }
+  const int32_t* sc = slot_col.data();
+  if (is_double) {
+    if (col_ptr_is_64) dev::EvalCscToSlots(static_cast<const int64_t*>(col_ptr), sc, indices, static_cast<const double*>(data), nelem, row0, rows, ns, static_cast<double*>(matrix));
+    else dev::EvalCscToSlots(static_cast<const int32_t*>(col_ptr), sc, indices, static_cast<const double*>(data), nelem, row0, rows, ns, static_cast<double*>(matrix));
+  } else {
+    if (col_ptr_is_64) dev::EvalCscToSlots(static_cast<const int64_t*>(col_ptr), sc, indices, static_cast<const float*>(data), nelem, row0, rows, ns, static_cast<float*>(matrix));
+    else dev::EvalCscToSlots(static_cast<const int32_t*>(col_ptr), sc, indices, static_cast<const float*>(data), nelem, row0, rows, ns, static_cast<float*>(matrix));
   }
 }
 

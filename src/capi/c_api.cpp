@@ -33,6 +33,7 @@
 #include "lgbm_amd/predictor.h"
 #include "lgbm_amd/random.h"
 #include "lgbm_amd/tuning.h"
+#include "../device/kernels.h"
 #include "../device/refit_quant.h"
 #include "../treelearner/growth_limits.h"
 
@@ -437,7 +438,7 @@ class Booster {
     return true;
   }
 
-  // whether a host matrix of nrow x ncol goes to the device (dense and CSR alike)
+  // whether a host matrix of nrow x ncol goes to the device (dense, CSR and CSC alike)
   bool DevicePredictGate(int data_type, int64_t nrow, int64_t ncol, int predict_type, const Config& cfg,
                          DevicePredictKind* kind) const {
     if (!DeviceKindOf(predict_type, kind)) return false;
@@ -501,6 +502,60 @@ class Booster {
     boosting_->CsrToSlotsOnHost(indptr, indptr_type == C_API_DTYPE_INT64, indices, data,
                                 data_type == C_API_DTYPE_FLOAT64, nindptr, nelem, start_iteration, num_iteration,
                                 num_used, used, matrix);
+  }
+
+  // CSC columns under the same gate (src/device/csc_kernels.hip): only the stored entries of the
+  // columns the trees split on go to the device
+  bool PredictCSCOnDevice(const void* col_ptr, int col_ptr_type, const int32_t* indices, const void* data,
+                          int data_type, int64_t ncol_ptr, int64_t nelem, int64_t num_row, int predict_type,
+                          int start_iteration, int num_iteration, const Config& cfg, double* out, int64_t* out_len) {
+    DevicePredictKind kind;
+    if (col_ptr_type != C_API_DTYPE_INT32 && col_ptr_type != C_API_DTYPE_INT64) return false;
+    if (!DevicePredictGate(data_type, num_row, ncol_ptr - 1, predict_type, cfg, &kind)) return false;
+    std::unique_lock<std::shared_mutex> l(mu_);
+    if (!boosting_->PredictCSCOnDevice(col_ptr, col_ptr_type == C_API_DTYPE_INT64, indices, data,
+                                       data_type == C_API_DTYPE_FLOAT64, ncol_ptr, nelem, num_row, start_iteration,
+                                       num_iteration, kind, out)) {
+      return false;
+    }
+    *out_len = num_row * boosting_->NumPredictOneRow(start_iteration, num_iteration, kind == DevicePredictKind::Leaf,
+                                                     kind == DevicePredictKind::Contrib);
+    return true;
+  }
+
+  // ... and CSC arrays in device memory, into device memory (ops.forest_predict on a sparse_csc tensor)
+  void PredictCSCDeviceBuffers(const void* d_col_ptr, int col_ptr_type, const int32_t* d_indices, const void* d_data,
+                               int data_type, int64_t ncol, int64_t nelem, int64_t nrow, int predict_type,
+                               int start_iteration, int num_iteration, double* d_out, int64_t out_len) {
+    DevicePredictKind kind;
+    if (!DeviceKindOf(predict_type, &kind) || kind == DevicePredictKind::Normal) {
+      Log::Fatal("forest prediction on device buffers: predict type %d is not raw, leaf or contrib", predict_type);
+    }
+    if (data_type != C_API_DTYPE_FLOAT32 && data_type != C_API_DTYPE_FLOAT64) {
+      Log::Fatal("forest prediction on device buffers: data must be float32 or float64");
+    }
+    if (col_ptr_type != C_API_DTYPE_INT32 && col_ptr_type != C_API_DTYPE_INT64) {
+      Log::Fatal("forest prediction on device buffers: col_ptr must be int32 or int64");
+    }
+    std::unique_lock<std::shared_mutex> l(mu_);
+    boosting_->PredictCSCDeviceBuffers(d_col_ptr, col_ptr_type == C_API_DTYPE_INT64, d_indices, d_data,
+                                       data_type == C_API_DTYPE_FLOAT64, ncol, nelem, nrow, start_iteration,
+                                       num_iteration, kind, d_out, out_len);
+  }
+
+  void CscToSlots(const void* col_ptr, int col_ptr_type, const int32_t* indices, const void* data, int data_type,
+                  int64_t ncol_ptr, int64_t nelem, int64_t num_row, int64_t row0, int64_t rows, int start_iteration,
+                  int num_iteration, int32_t* num_used, int32_t* used, void* matrix) {
+    if (col_ptr_type != C_API_DTYPE_INT32 && col_ptr_type != C_API_DTYPE_INT64) Log::Fatal("Unknown col_ptr type");
+    if (data_type != C_API_DTYPE_FLOAT32 && data_type != C_API_DTYPE_FLOAT64) Log::Fatal("Unknown data type in CSC");
+    if (ncol_ptr < 1 || nelem < 0 || row0 < 0 || rows < 0 || row0 + rows > num_row) {
+      Log::Fatal("CSC slots: rows [%lld, %lld) of %lld, %lld pointer entries", static_cast<long long>(row0),
+                 static_cast<long long>(row0 + rows), static_cast<long long>(num_row), static_cast<long long>(ncol_ptr));
+    }
+    std::unique_lock<std::shared_mutex> l(mu_);
+    boosting_->CscToSlotsOnHost(col_ptr, col_ptr_type == C_API_DTYPE_INT64, indices, data,
+                                data_type == C_API_DTYPE_FLOAT64, ncol_ptr, nelem, row0, rows, start_iteration,
+                                num_iteration, num_used, used, matrix);
   }
 
   // raw scores, leaf indices or contributions of a row-major matrix in device memory, into
@@ -1201,7 +1256,10 @@ int LGBM_BoosterPredictSparseOutput(BoosterHandle handle, const void* indptr, in
   } else if (matrix_type == C_API_MATRIX_TYPE_CSC) {
     nrow = num_col_or_row;
     ncol = nindptr - 1;
-    rows = CSCToRows(indptr, indptr_type, indices, data, data_type, nindptr, nrow);
+    dense.resize(static_cast<size_t>(nrow) * width);
+    on_device = b->PredictCSCOnDevice(indptr, indptr_type, indices, data, data_type, nindptr, nelem, nrow,
+                                      predict_type, start_iteration, num_iteration, cfg, dense.data(), &dl);
+    if (!on_device) rows = CSCToRows(indptr, indptr_type, indices, data, data_type, nindptr, nrow);
   } else {
     Log::Fatal("Unknown matrix type in LGBM_BoosterPredictSparseOutput");
   }
@@ -1322,11 +1380,16 @@ int LGBM_BoosterPredictForCSRSingleRowFast(FastConfigHandle fastConfig_handle, c
 }
 
 int LGBM_BoosterPredictForCSC(BoosterHandle handle, const void* col_ptr, int col_ptr_type, const int32_t* indices,
-                              const void* data, int data_type, int64_t ncol_ptr, int64_t, int64_t num_row,
+                              const void* data, int data_type, int64_t ncol_ptr, int64_t nelem, int64_t num_row,
                               int predict_type, int start_iteration, int num_iteration, const char* parameter,
                               int64_t* out_len, double* out_result) {
   API_BEGIN();
   Config cfg = ParamsToConfig(parameter);
+  if (static_cast<Booster*>(handle)->PredictCSCOnDevice(col_ptr, col_ptr_type, indices, data, data_type, ncol_ptr,
+                                                        nelem, num_row, predict_type, start_iteration, num_iteration,
+                                                        cfg, out_result, out_len)) {
+    return 0;
+  }
   auto rows = CSCToRows(col_ptr, col_ptr_type, indices, data, data_type, ncol_ptr, num_row);
   static_cast<Booster*>(handle)->PredictRows([&rows](int64_t r) { return rows[r]; }, num_row, ncol_ptr - 1,
                                               predict_type, start_iteration, num_iteration, cfg, out_result, out_len);
@@ -1606,6 +1669,25 @@ int LGBM_AMD_CsrToSlots(BoosterHandle handle, const void* indptr, int indptr_typ
   API_END();
 }
 
+int LGBM_AMD_CscToSlots(BoosterHandle handle, const void* col_ptr, int col_ptr_type, const int32_t* indices,
+                        const void* data, int data_type, int64_t ncol_ptr, int64_t nelem, int64_t num_row, int64_t row0,
+                        int64_t rows, int start_iteration, int num_iteration, int32_t* out_num_used, int32_t* out_used,
+                        void* out_matrix) {
+  API_BEGIN();
+  static_cast<Booster*>(handle)->CscToSlots(col_ptr, col_ptr_type, indices, data, data_type, ncol_ptr, nelem, num_row,
+                                            row0, rows, start_iteration, num_iteration, out_num_used, out_used,
+                                            out_matrix);
+  API_END();
+}
+
+int LGBM_AMD_CscLaunchInfo(int64_t* out) {
+  API_BEGIN();
+  out[0] = dev::kCscSegmentEntries;
+  out[1] = dev::kCscThreads;
+  out[2] = 64;
+  API_END();
+}
+
 int LGBM_AMD_RefitLeafSums(const int32_t* leaf, const float* grad, const float* hess, int64_t n, int32_t num_leaves,
                            double* out_sums, int64_t* out_counts, int32_t* out_scale_exp) {
   API_BEGIN();
@@ -1652,6 +1734,15 @@ void BoosterPredictCSRDeviceBuffers(BoosterHandle handle, const void* d_indptr, 
   static_cast<Booster*>(handle)->PredictCSRDeviceBuffers(d_indptr, indptr_type, d_indices, d_data, data_type, nrow,
                                                          nelem, predict_type, start_iteration, num_iteration, d_out,
                                                          out_len);
+}
+// (LGBMAMD_OpForestPredictCSC)
+void BoosterPredictCSCDeviceBuffers(BoosterHandle handle, const void* d_col_ptr, int col_ptr_type,
+                                    const int32_t* d_indices, const void* d_data, int data_type, int64_t ncol,
+                                    int64_t nelem, int64_t nrow, int predict_type, int start_iteration,
+                                    int num_iteration, double* d_out, int64_t out_len) {
+  static_cast<Booster*>(handle)->PredictCSCDeviceBuffers(d_col_ptr, col_ptr_type, d_indices, d_data, data_type, ncol,
+                                                         nelem, nrow, predict_type, start_iteration, num_iteration,
+                                                         d_out, out_len);
 }
 }  // namespace lgbm_amd
 

@@ -42,6 +42,10 @@ void BoosterPredictCSRDeviceBuffers(BoosterHandle handle, const void* d_indptr, 
                                     const int32_t* d_indices, const void* d_data, int data_type, int64_t nrow,
                                     int64_t nelem, int predict_type, int start_iteration, int num_iteration,
                                     double* d_out, int64_t out_len);
+void BoosterPredictCSCDeviceBuffers(BoosterHandle handle, const void* d_col_ptr, int col_ptr_type,
+                                    const int32_t* d_indices, const void* d_data, int data_type, int64_t ncol,
+                                    int64_t nelem, int64_t nrow, int predict_type, int start_iteration,
+                                    int num_iteration, double* d_out, int64_t out_len);
 }  // namespace lgbm_amd
 
 namespace {
@@ -180,6 +184,21 @@ LIGHTGBM_C_EXPORT int LGBMAMD_OpForestPredictCSR(BoosterHandle handle, const voi
                                                  int num_iteration, double* d_out, int64_t out_len) {
   return Guard([&] {
     BoosterPredictCSRDeviceBuffers(handle, d_indptr, indptr_type, d_indices, d_data, data_type, nrow, nelem,
+                                   predict_type, start_iteration, num_iteration, d_out, out_len);
+  });
+}
+
+// ... and of the nrow rows of a CSC matrix in device memory (d_col_ptr: ncol + 1 int32 / int64
+// entries; d_indices: the int32 row of each of the nelem entries; d_data: float32 / float64
+// values): the columns the trees split on are scattered into the compact matrix
+// (src/device/csc_kernels.hip).  An entry whose row is outside [0, nrow) is dropped
+LIGHTGBM_C_EXPORT int LGBMAMD_OpForestPredictCSC(BoosterHandle handle, const void* d_col_ptr, int col_ptr_type,
+                                                 const int32_t* d_indices, const void* d_data, int data_type,
+                                                 int64_t ncol, int64_t nelem, int64_t nrow, int predict_type,
+                                                 int start_iteration, int num_iteration, double* d_out,
+                                                 int64_t out_len) {
+  return Guard([&] {
+    BoosterPredictCSCDeviceBuffers(handle, d_col_ptr, col_ptr_type, d_indices, d_data, data_type, ncol, nelem, nrow,
                                    predict_type, start_iteration, num_iteration, d_out, out_len);
   });
 }

@@ -638,6 +638,32 @@ struct CsrSlotsArgs {
 };
 void CsrToSlots(const CsrSlotsArgs& c, hipStream_t s);
 
+// CSC columns into the same compact matrix for the chunk of rows [row0, row0 + num_rows)
+// (src/device/csc_slots.h has the rule of an entry; src/device/csc_kernels.hip): a slot's values
+// are the stored entries of one column.  CscColumnOrder writes `ascending` once for arrays that
+// stay on the device; CscToSlots, on the same stream, zero-fills the matrix and scatters a chunk.
+// A column is cut into segments of kCscSegmentEntries stored entries, one wave each; a column
+// whose row indices do not ascend strictly is walked by one wave in stored order
+constexpr int kCscThreads = 256;
+constexpr int kCscSegmentEntries = 512;
+struct CscSlotsArgs {
+  int32_t col_ptr_is_64{};   // col_ptr: int64 (else int32)
+  int32_t is_double{};       // data and out: float64 (else float32)
+  int32_t num_slots{};
+  int32_t pad{};
+  int64_t num_entries{};     // entries of indices / data (columns are clamped to them)
+  int64_t row0{};            // first row of the chunk
+  int64_t num_rows{};        // rows of the chunk: the matrix's column stride
+  const void* col_ptr{};
+  const int32_t* slot_col{};  // [num_slots] index into col_ptr of the slot's column, -1: none
+  const int32_t* indices{};   // row of each entry
+  const void* data{};
+  uint32_t* ascending{};      // [num_slots] non-zero: the column's row indices ascend strictly
+  void* out{};
+};
+void CscColumnOrder(const CscSlotsArgs& c, hipStream_t s);
+void CscToSlots(const CscSlotsArgs& c, hipStream_t s);
+
 // validation metrics on device scores (one model per iteration)
 constexpr int kMetricL2 = 1, kMetricRMSE = 2, kMetricL1 = 3, kMetricBinLogloss = 4, kMetricBinError = 5,
               kMetricAUC = 6, kMetricQuantile = 7, kMetricHuber = 8, kMetricFair = 9, kMetricPoisson = 10,

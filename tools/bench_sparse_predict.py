@@ -6,6 +6,13 @@ indices and SHAP contributions, through Booster.predict, in seconds:
           before device CSR prediction
   dense   X.toarray() (timed, its own figure) and the dense device path on the result
   csr     the device path on the CSR matrix (src/device/csr_kernels.hip and the forest kernels)
+  csc_host   the host predictor on the same matrix as CSC (converted once, outside the timed
+          region): the transposition into rows, then the host predictor -- what a CSC input cost
+          before device CSC prediction
+  tocsr_csr  m.tocsr() inside the timed region, then the device CSR path: what a Python caller
+          could do instead
+  csc     the device path on the CSC matrix (src/device/csc_kernels.hip and the forest kernels);
+          --shuffle-column stores one used column of it in shuffled order (the single-wave path)
 
   python tools/bench_sparse_predict.py
   python tools/bench_sparse_predict.py --rows 100000 --kinds raw --paths csr
@@ -16,7 +23,9 @@ indices and SHAP contributions, through Booster.predict, in seconds:
 Contributions are rows x (columns + 1) doubles (16 GB at the default shape) on every path, so
 they are measured on --contrib-rows rows.  Every path is warmed up once, then timed --repeats
 times (median); a run slower than --slow-s is not repeated.  Prints one JSON line; "equal"
-tells whether the csr path's raw scores and leaf indices equalled the host's and the dense path's.
+tells whether the csr path's raw scores and leaf indices equalled the host's and the dense path's,
+and the csc path's those of every other path measured; "copied_bytes" is what the csr and csc
+device paths copy to the device per call.
 """
 import argparse
 import ctypes
@@ -78,7 +87,10 @@ def main():
     ap.add_argument("--trees", type=int, default=100)
     ap.add_argument("--leaves", type=int, default=63)
     ap.add_argument("--kinds", nargs="*", default=["raw", "leaf", "contrib"], choices=list(PRED))
-    ap.add_argument("--paths", nargs="*", default=["host", "dense", "csr"], choices=["host", "dense", "csr"])
+    ap.add_argument("--paths", nargs="*", default=["host", "dense", "csr"],
+                    choices=["host", "dense", "csr", "csc_host", "tocsr_csr", "csc"])
+    ap.add_argument("--shuffle-column", action="store_true",
+                    help="store the longest used column of the CSC matrix in shuffled order")
     ap.add_argument("--repeats", type=int, default=3)
     ap.add_argument("--slow-s", type=float, default=20.0)
     ap.add_argument("--host-threads", type=int, default=16)
@@ -116,10 +128,54 @@ def main():
             raise SystemExit("the prediction did not run on the device")
         return r
 
+    want_csc = any(p in args.paths for p in ("csc_host", "tocsr_csr", "csc"))
+    csc_of = {}
+
+    def as_csc(M):
+        """M as CSC, converted once per matrix outside every timed region"""
+        if id(M) not in csc_of:
+            C = M.tocsc()
+            if args.shuffle_column:
+                cols = np.nonzero(bst.feature_importance())[0]
+                c = cols[np.argmax(np.diff(C.indptr)[cols])]
+                lo, hi = C.indptr[c], C.indptr[c + 1]
+                perm = np.random.RandomState(4).permutation(hi - lo) + lo
+                C.indices[lo:hi], C.data[lo:hi] = C.indices[perm], C.data[perm]
+                C.has_sorted_indices = False
+                result["shuffled_column_entries"] = int(hi - lo)
+            csc_of[id(M)] = C
+        return csc_of[id(M)]
+
+    def copied_bytes(M, C):
+        """bytes the device paths copy to the device per call: every stored entry and the row
+        pointer (csr), the stored entries of the used columns and their pointer (csc)"""
+        cols = np.nonzero(bst.feature_importance())[0]
+        per = 4 + M.data.dtype.itemsize
+        return {"csr": int(M.nnz * per + M.indptr.nbytes),
+                "csc": int(np.diff(C.indptr)[cols].sum() * per + 8 * (len(cols) + 1) + 4 * len(cols))}
+
     for kind in args.kinds:
         M = X if kind != "contrib" else X[:args.contrib_rows]
         row = {"rows": M.shape[0]}
         outs = {}
+        if want_csc:
+            C = as_csc(M)
+            row["copied_bytes"] = copied_bytes(M, C)
+        if "csc" in args.paths:
+            t, k, outs["csc"] = on_device(lambda: bst.predict(C, **PRED[kind], **gpu))
+            row["csc"] = {"seconds": t, "runs": k}
+        if "tocsr_csr" in args.paths:
+            t, k, outs["tocsr_csr"] = on_device(lambda: bst.predict(C.tocsr(), **PRED[kind], **gpu))
+            row["tocsr_csr"] = {"seconds": t, "runs": k}
+            t, k, _ = timed(C.tocsr, args.repeats, args.slow_s)
+            row["tocsr"] = {"seconds": t, "runs": k}
+        if "csc_host" in args.paths:
+            os.environ["LGBM_AMD_HOST_PREDICT"] = "1"
+            try:
+                t, k, outs["csc_host"] = timed(lambda: bst.predict(C, **PRED[kind], **gpu), args.repeats, args.slow_s)
+            finally:
+                del os.environ["LGBM_AMD_HOST_PREDICT"]
+            row["csc_host"] = {"seconds": t, "runs": k}
         if "csr" in args.paths:
             t, k, outs["csr"] = on_device(lambda: bst.predict(M, **PRED[kind], **gpu))
             row["csr"] = {"seconds": t, "runs": k}
@@ -139,6 +195,10 @@ def main():
         if kind != "contrib" and "csr" in outs:
             for other in ("host", "dense"):
                 if other in outs and not np.array_equal(outs["csr"], outs[other]):
+                    result["equal"] = False
+        if kind != "contrib" and "csc" in outs:
+            for other in ("csc_host", "tocsr_csr", "csr", "host", "dense"):
+                if other in outs and not np.array_equal(outs["csc"], outs[other]):
                     result["equal"] = False
         result["kinds"][kind] = row
         print("# %s: %s" % (kind, json.dumps(row)), file=sys.stderr, flush=True)
