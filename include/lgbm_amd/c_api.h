@@ -294,6 +294,22 @@ LIGHTGBM_C_EXPORT int LGBM_AMD_RefitLeafSums(const int32_t* leaf, const float* g
 // too and are not read) grows a tree -- the GrowthPlan as a JSON object
 LIGHTGBM_C_EXPORT int LGBM_AMD_GrowthPlan(const char* parameters, const char* facts_json, int64_t buffer_len,
                                           int64_t* out_len, char* out_str);
+// the rule of one CSR row of the device binning (src/device/csr_bins.h) evaluated on the host
+// with a constructed dataset's bin mappers (no GPU): bins is row-major [nindptr - 1][*num_groups],
+// the layout of LGBM_AMD_DatasetGetGroupBins, with -1 in the columns of groups that have a
+// categorical member (they are binned on the host).  Entries on a negative column, on one not
+// below the dataset's num_total_features or on an unused feature are dropped; indptr is clamped
+// to [0, nelem].  With bins or indptr null only *num_groups is returned
+LIGHTGBM_C_EXPORT int LGBM_AMD_CsrToGroupBins(DatasetHandle handle, const void* indptr, int indptr_type,
+                                              const int32_t* indices, const void* data, int data_type,
+                                              int64_t nindptr, int64_t nelem, int32_t* bins, int* num_groups);
+// the launch shape of the CSR binning (src/device/csr_bin_kernels.hip; tests place rows on its
+// boundaries): out[0] the stored entries a wave reads per batch, out[1] the rows of a workgroup,
+// out[2] the rows of a compaction tile, out[3] the most features whose zeros are pushed
+LIGHTGBM_C_EXPORT int LGBM_AMD_CsrBinLaunchInfo(int64_t* out);
+// matrices this process has binned on the device: dense (LGBM_DatasetCreateFromMat) and CSR
+// (LGBM_DatasetCreateFromCSR); tests: whether a construction took the device path
+LIGHTGBM_C_EXPORT int LGBM_AMD_DeviceBinStats(int64_t* dense_calls, int64_t* csr_calls);
 // predictions this process has computed on the device, over all boosters (tests: whether a call
 // took the device path or the host predictor)
 LIGHTGBM_C_EXPORT int LGBM_AMD_DevicePredictCount(int64_t* out);

@@ -153,6 +153,10 @@ class Dataset {
 
   void PushDenseRow(data_size_t row, const double* values, int ncol);
   void PushSparseRow(data_size_t row, const std::vector<std::pair<int, double>>& values);
+  // ... of the groups with done_group[g] == 0 only: the others were written whole elsewhere (the
+  // device binning of a CSR matrix); groups are independent, so the split is exact
+  void PushSparseRowOfGroups(data_size_t row, const std::vector<std::pair<int, double>>& values,
+                             const std::vector<char>& done_group);
   void PushColumnValue(data_size_t row, int real_col, double value);
   // every push is done: sparse groups merge their per-thread push buffers
   void FinishLoad();

@@ -1,5 +1,5 @@
-// Value -> bin mapping of dense matrices on the device (src/device/bin_kernels.hip;
-// reference include/LightGBM/bin.h:132 ValueToBin).
+// Value -> bin mapping of dense and CSR matrices on the device (src/device/bin_kernels.hip,
+// src/device/csr_bin_kernels.hip; reference include/LightGBM/bin.h:132 ValueToBin).
 #pragma once
 
 #include <cstdint>
@@ -11,6 +11,10 @@ namespace lgbm_amd {
 
 class Dataset;
 
+// the HIP device a dataset under `cfg` is binned on (gpu_device_id, else LOCAL_RANK, else 0), or
+// -1: none visible
+int BinningDevice(const Config& cfg);
+
 // device binning for an nrow x ncol matrix: LGBM_AMD_DEVICE_BINNING=0 never, =1 whenever a HIP
 // device is visible, otherwise for device_type=gpu and at least 4M values
 bool UseDeviceBinning(const Config& cfg, int64_t nrow, int64_t ncol);
@@ -20,5 +24,40 @@ bool UseDeviceBinning(const Config& cfg, int64_t nrow, int64_t ncol);
 // rows on the host.  Returns per column whether it was handled (the caller pushes the rest).
 std::vector<char> DeviceBinDenseMatrix(Dataset* ds, const void* data, bool is_f64, int32_t nrow, int32_t ncol,
                                        bool row_major, const Config& cfg);
+
+// device binning for a CSR matrix of nelem stored entries: the same knob; without it,
+// device_type=gpu and at least kCsrBinMinEntries stored entries.  (The device path was ahead at
+// every size timed, down to 60K entries; from 1M entries on it is ahead by more than the
+// run-to-run spread of a construction of a few milliseconds: profiles/r13_device_sparse_binning.md)
+constexpr int64_t kCsrBinMinEntries = int64_t{1} << 20;
+bool UseDeviceBinningCsr(const Config& cfg, int64_t nelem);
+
+// Writes every group whose members are all numerical into `ds` from the rows of a CSR matrix
+// (indptr: nrow + 1 entries, C_API_DTYPE_INT32 / INT64; data: nelem values, C_API_DTYPE_FLOAT32 /
+// FLOAT64), bit-identical to Dataset::PushSparseRow of every row on the host: dense groups get
+// their column, sparse groups their stored rows and bins appended chunk by chunk.  Returns per
+// group of the dataset whether it was handled (the caller pushes the entries of the other groups);
+// nothing is handled when no device is visible, indptr is not a non-decreasing sequence inside
+// [0, nelem], or more than kMaxPushZeroFeatures features need their zeros pushed.
+std::vector<char> DeviceBinCsrMatrix(Dataset* ds, const void* indptr, int indptr_type, const int32_t* indices,
+                                     const void* data, int data_type, int64_t nrow, int64_t nelem, const Config& cfg);
+
+// The rule of one CSR row (src/device/csr_bins.h) on the host with the dataset's mappers:
+// bins[nrow][ds.num_groups()], -1 in the columns of groups with a categorical member.  No GPU.
+void EvalCsrGroupBins(const Dataset& ds, const void* indptr, int indptr_type, const int32_t* indices,
+                      const void* data, int data_type, int64_t nrow, int64_t nelem, int32_t* bins);
+
+// ... and by k_csr_to_group_bins on CSR arrays in device memory, into d_bins (device, the same
+// layout), on the current device's null stream; returns after it finished
+void CsrGroupBinsOnDevice(const Dataset& ds, const void* d_indptr, int indptr_type, const int32_t* d_indices,
+                          const void* d_data, int data_type, int64_t nrow, int64_t nelem, int32_t* d_bins);
+
+// out[0]: stored entries a wave reads per batch; out[1]: rows per workgroup; out[2]: rows per
+// compaction tile; out[3]: kMaxPushZeroFeatures
+void CsrBinLaunchInfo(int64_t* out);
+
+// how many matrices went through DeviceBinDenseMatrix / DeviceBinCsrMatrix in this process
+void DeviceBinStats(int64_t* dense_calls, int64_t* csr_calls);
+void NoteDeviceBinCall(bool csr);  // (the two paths count themselves)
 
 }  // namespace lgbm_amd

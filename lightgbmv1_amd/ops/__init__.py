@@ -23,6 +23,10 @@ the kernels can be checked one by one against plain PyTorch references
   (src/device/refit_kernels.hip; reference SerialTreeLearner::FitByExistingTree): exact
   fixed-point per-leaf sums of gradients and hessians over a column of leaf indices, and
   ``score += values[leaf]``; :func:`refit_launch_info` gives their launch shape
+* :func:`csr_group_bins` -- the group bins of CSR rows under a constructed Dataset's bin mappers,
+  by the kernel that bins a scipy CSR matrix when a Dataset is constructed with
+  ``device_type=gpu`` (src/device/csr_bin_kernels.hip; reference Dataset::PushOneRow);
+  :func:`csr_bin_launch_info` gives its launch shape
 
 There is no host fallback: the ops need a GPU and the in-tree library.
 """
@@ -34,7 +38,7 @@ from .._native import LightGBMError, call as _native_call, params_str as param_d
 from ..basic import _load_lib
 
 __all__ = ["gradients", "metric", "sample_rows", "forest_predict", "leaf_sums", "add_leaf_values",
-           "refit_launch_info", "csc_launch_info"]
+           "refit_launch_info", "csc_launch_info", "csr_group_bins", "csr_bin_launch_info"]
 
 
 def _torch():
@@ -267,6 +271,47 @@ def csc_launch_info():
     out = (ctypes.c_int64 * 3)()
     _native_call("LGBM_AMD_CscLaunchInfo", out)
     return {"segment_entries": out[0], "block": out[1], "batch": out[2]}
+
+
+def csr_bin_launch_info():
+    """The launch shape of the CSR binning kernels (src/device/csr_bin_kernels.hip): ``batch`` (the
+    stored entries of a row that its wave reads at a time), ``rows_per_block`` (rows of a
+    workgroup), ``tile_rows`` (rows per tile of the compaction of sparse groups) and
+    ``max_push_zero_features`` (with more features whose default bin is not their most frequent
+    bin a matrix is binned on the host)."""
+    out = (ctypes.c_int64 * 4)()
+    _native_call("LGBM_AMD_CsrBinLaunchInfo", out)
+    return {"batch": out[0], "rows_per_block": out[1], "tile_rows": out[2], "max_push_zero_features": out[3]}
+
+
+def csr_group_bins(dataset, X):
+    """The group bins of the rows of ``X``, a ``torch.sparse_csr`` GPU tensor with float32 or float64
+    values (int32 or int64 ``crow_indices``; int64 ``col_indices`` are converted to int32 on the
+    device), under the bin mappers of the constructed ``dataset``: an int32 GPU tensor
+    ``[rows, groups]`` in the layout of ``LGBM_AMD_DatasetGetGroupBins``, with -1 in the columns of
+    groups that have a categorical member (those are binned on the host).  Entries on columns the
+    dataset does not have are dropped, and of several writes to one cell the last stored wins."""
+    torch = _torch()
+    if not isinstance(X, torch.Tensor) or X.layout != torch.sparse_csr or X.dim() != 2 or \
+            X.dtype not in (torch.float32, torch.float64):
+        raise LightGBMError("X must be a 2-d float32 or float64 torch.sparse_csr tensor on the GPU")
+    handle = dataset.construct().handle
+    crow, values = X.crow_indices().contiguous(), X.values().contiguous()
+    if crow.dtype not in (torch.int32, torch.int64):
+        raise LightGBMError("crow_indices must be int32 or int64")
+    col = X.col_indices().to(torch.int32).contiguous()
+    ng = ctypes.c_int(0)
+    _native_call("LGBM_AMD_DatasetGetGroupBins", handle, None, None, ctypes.byref(ng))
+    n = X.shape[0]
+    out = torch.empty((n, ng.value), dtype=torch.int32, device=X.device)
+    torch.cuda.synchronize(X.device)
+    with torch.cuda.device(X.device):
+        _check(_lib().LGBMAMD_OpCsrGroupBins(
+            handle, _dev_ptr(crow, crow.dtype, "crow_indices"), ctypes.c_int(2 if crow.dtype == torch.int32 else 3),
+            _dev_ptr(col, torch.int32, "col_indices"), _dev_ptr(values, X.dtype, "values"),
+            ctypes.c_int(0 if X.dtype == torch.float32 else 1), ctypes.c_int64(n), ctypes.c_int64(values.numel()),
+            _dev_ptr(out, torch.int32, "out")))
+    return out
 
 
 def leaf_sums(leaf, grad, hess, num_leaves):

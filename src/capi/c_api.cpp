@@ -7,6 +7,7 @@
 #include <hip/hip_runtime_api.h>
 #include <omp.h>
 
+#include <algorithm>
 #include <cmath>
 #include <cstdlib>
 #include <cstring>
@@ -196,9 +197,12 @@ Dataset* ConstructFromSamples(std::vector<std::vector<double>>* sv, std::vector<
   return ds.release();
 }
 
-// build a dataset from a row accessor: sample -> bins -> parallel push
+// build a dataset from a row accessor: sample -> bins -> parallel push.  device_bin (or none):
+// called once the bin mappers exist, it writes whole groups itself and returns which (the
+// device binning of a CSR matrix); the rows then push the entries of the other groups only
 Dataset* DatasetFromRows(const std::function<Row(int64_t)>& get_row, data_size_t nrow, int ncol, const Config& cfg,
-                         const Dataset* reference) {
+                         const Dataset* reference,
+                         const std::function<std::vector<char>(Dataset*)>& device_bin = nullptr) {
   std::unique_ptr<Dataset> ds;
   if (reference == nullptr) {
     auto idx = SampleRows(cfg, nrow);
@@ -223,10 +227,20 @@ Dataset* DatasetFromRows(const std::function<Row(int64_t)>& get_row, data_size_t
     ds->CreateValid(*reference, nrow);
     ds->metadata().Init(nrow, false, false);
   }
+  std::vector<char> done;
+  if (device_bin) done = device_bin(ds.get());
+  const size_t num_done = static_cast<size_t>(std::count(done.begin(), done.end(), 1));
   common::OmpErrors errors;
+  if (num_done == 0) {
 #pragma omp parallel for schedule(static)
-  for (int64_t r = 0; r < nrow; ++r) {
-    errors.Run([&] { ds->PushSparseRow(static_cast<data_size_t>(r), get_row(r)); });
+    for (int64_t r = 0; r < nrow; ++r) {
+      errors.Run([&] { ds->PushSparseRow(static_cast<data_size_t>(r), get_row(r)); });
+    }
+  } else if (num_done < done.size()) {
+#pragma omp parallel for schedule(static)
+    for (int64_t r = 0; r < nrow; ++r) {
+      errors.Run([&] { ds->PushSparseRowOfGroups(static_cast<data_size_t>(r), get_row(r), done); });
+    }
   }
   errors.Check();
   ds->FinishLoad();
@@ -749,8 +763,14 @@ int LGBM_DatasetCreateFromCSR(const void* indptr, int indptr_type, const int32_t
   if (num_col >= INT32_MAX) Log::Fatal("The number of columns should be smaller than INT32_MAX.");
   Config cfg = ParamsToConfig(parameters);
   auto get = CSRRowFun(indptr, indptr_type, indices, data, data_type, nindptr, nelem);
+  // numerical groups binned on the device (device_type=gpu, enough stored entries); the column
+  // count may have grown while sampling: the dataset's num_total_features is what the tables cover
+  auto device_bin = [&](Dataset* ds) {
+    if (!UseDeviceBinningCsr(cfg, nelem)) return std::vector<char>();
+    return DeviceBinCsrMatrix(ds, indptr, indptr_type, indices, data, data_type, nindptr - 1, nelem, cfg);
+  };
   *out = DatasetFromRows(get, static_cast<data_size_t>(nindptr - 1), static_cast<int>(num_col), cfg,
-                         static_cast<const Dataset*>(reference));
+                         static_cast<const Dataset*>(reference), device_bin);
   API_END();
 }
 
@@ -1709,6 +1729,30 @@ int LGBM_AMD_GrowthPlan(const char* parameters, const char* facts_json, int64_t 
   const std::string plan = GrowthPlanToJson(PlanGrowth(config, facts));
   *out_len = static_cast<int64_t>(plan.size()) + 1;
   if (buffer_len >= *out_len) std::memcpy(out_str, plan.c_str(), plan.size() + 1);
+  API_END();
+}
+
+int LGBM_AMD_CsrToGroupBins(DatasetHandle handle, const void* indptr, int indptr_type, const int32_t* indices,
+                            const void* data, int data_type, int64_t nindptr, int64_t nelem, int32_t* bins,
+                            int* num_groups) {
+  API_BEGIN();
+  const Dataset* d = static_cast<const Dataset*>(handle);
+  *num_groups = d->num_groups();
+  if (bins != nullptr && indptr != nullptr) {
+    EvalCsrGroupBins(*d, indptr, indptr_type, indices, data, data_type, nindptr - 1, nelem, bins);
+  }
+  API_END();
+}
+
+int LGBM_AMD_CsrBinLaunchInfo(int64_t* out) {
+  API_BEGIN();
+  CsrBinLaunchInfo(out);
+  API_END();
+}
+
+int LGBM_AMD_DeviceBinStats(int64_t* dense_calls, int64_t* csr_calls) {
+  API_BEGIN();
+  DeviceBinStats(dense_calls, csr_calls);
   API_END();
 }
 

@@ -7,7 +7,8 @@
 // their numerics can be checked against plain PyTorch / NumPy references (tests/test_ops.py,
 // tests/test_rank_ops.py); a booster's forest prediction (scores, leaf indices, SHAP
 // contributions) on a matrix that already is on the device; and the two per-tree passes of a
-// device refit (src/device/refit_kernels.hip: per-leaf sums, score update; tests/test_device_refit.py).
+// device refit (src/device/refit_kernels.hip: per-leaf sums, score update; tests/test_device_refit.py);
+// and the CSR binning kernel under a dataset's bin mappers (src/device/csr_bin_kernels.hip).
 //
 // Objectives and metrics are created from a parameter string exactly as training creates
 // them (reference objective_function.cpp:16-56, metric.cpp:16-63), so the kernels see the
@@ -26,6 +27,7 @@
 #include "lgbm_amd/c_api.h"
 #include "lgbm_amd/config.h"
 #include "lgbm_amd/dataset.h"
+#include "lgbm_amd/device_binning.h"
 #include "lgbm_amd/log.h"
 #include "lgbm_amd/tuning.h"
 #include "lgbm_amd/metric.h"
@@ -200,6 +202,19 @@ LIGHTGBM_C_EXPORT int LGBMAMD_OpForestPredictCSC(BoosterHandle handle, const voi
   return Guard([&] {
     BoosterPredictCSCDeviceBuffers(handle, d_col_ptr, col_ptr_type, d_indices, d_data, data_type, ncol, nelem, nrow,
                                    predict_type, start_iteration, num_iteration, d_out, out_len);
+  });
+}
+
+// the group bins of nrow CSR rows in device memory under a constructed dataset's bin mappers, by
+// the kernel of LGBM_DatasetCreateFromCSR's device path (src/device/csr_bin_kernels.hip
+// k_csr_to_group_bins): d_bins (device, int32) is row-major [nrow][groups of the dataset], -1 in
+// the columns of groups with a categorical member -- the matrix of LGBM_AMD_CsrToGroupBins
+LIGHTGBM_C_EXPORT int LGBMAMD_OpCsrGroupBins(DatasetHandle handle, const void* d_indptr, int indptr_type,
+                                             const int32_t* d_indices, const void* d_data, int data_type,
+                                             int64_t nrow, int64_t nelem, int32_t* d_bins) {
+  return Guard([&] {
+    CsrGroupBinsOnDevice(*static_cast<const Dataset*>(handle), d_indptr, indptr_type, d_indices, d_data, data_type,
+                         nrow, nelem, d_bins);
   });
 }
 

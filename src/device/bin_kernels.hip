@@ -12,10 +12,12 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <atomic>
 #include <cmath>
 #include <cstdlib>
 #include <vector>
 
+#include "csr_bins.h"
 #include "lgbm_amd/dataset.h"
 #include "lgbm_amd/device_binning.h"
 #include "lgbm_amd/log.h"
@@ -75,24 +77,10 @@ __global__ __launch_bounds__(kBinThreads) void k_value_to_bin(const T* x, int ro
     uint32_t v = 0;
     for (int f = G.fbegin; f < G.fend; ++f) {
       const BinFeat F = feats[f];
-      double value = static_cast<double>(xr[cs * F.col]);
-      int bin;
-      if (isnan(value) && F.nan_bin >= 0) {
-        bin = F.nan_bin;
-      } else {
-        if (isnan(value)) value = 0.0;
-        const double* u = staged ? s_ub + (F.ub_off - ub_lo) : ub + F.ub_off;
-        int lo = 0, hi = F.hi;
-        while (lo < hi) {
-          const int mid = (lo + hi - 1) / 2;
-          if (value <= u[mid]) hi = mid;
-          else lo = mid + 1;
-        }
-        bin = lo;
-      }
-      if (bin == F.mfb) continue;
-      if (F.mfb == 0) bin -= 1;
-      v = static_cast<uint32_t>(bin) + F.goff;
+      const double value = static_cast<double>(xr[cs * F.col]);
+      const double* u = staged ? s_ub + (F.ub_off - ub_lo) : ub + F.ub_off;
+      // (the per-value rule of src/device/csr_bins.h, shared with the CSR kernel)
+      dev::GroupCellOfBin(dev::ValueToBinNumerical(value, F.hi, F.nan_bin, u), F.mfb, F.goff, &v);
     }
     uint8_t* o = out + G.out_off;
     if (G.bytes == 1) o[r] = static_cast<uint8_t>(v);
@@ -101,6 +89,18 @@ __global__ __launch_bounds__(kBinThreads) void k_value_to_bin(const T* x, int ro
   }
 }
 
+std::atomic<int64_t> g_bin_calls[2];  // dense, CSR
+
+}  // namespace
+
+void NoteDeviceBinCall(bool csr) { g_bin_calls[csr ? 1 : 0].fetch_add(1, std::memory_order_relaxed); }
+
+void DeviceBinStats(int64_t* dense_calls, int64_t* csr_calls) {
+  if (dense_calls != nullptr) *dense_calls = g_bin_calls[0].load(std::memory_order_relaxed);
+  if (csr_calls != nullptr) *csr_calls = g_bin_calls[1].load(std::memory_order_relaxed);
+}
+
+// the HIP device of a dataset construction under `cfg`, or -1: none visible
 int BinningDevice(const Config& cfg) {
   int count = 0;
   if (hipGetDeviceCount(&count) != hipSuccess || count <= 0) {
@@ -112,7 +112,13 @@ int BinningDevice(const Config& cfg) {
   return 0;
 }
 
-}  // namespace
+bool UseDeviceBinningCsr(const Config& cfg, int64_t nelem) {
+  const char* e = tuning::Get(tuning::Knob::DeviceBinning);
+  if (e != nullptr && e[0] == '0') return false;
+  const bool forced = e != nullptr && e[0] == '1';
+  if (!forced && (cfg.device_type != "gpu" || nelem < kCsrBinMinEntries)) return false;
+  return BinningDevice(cfg) >= 0;
+}
 
 bool UseDeviceBinning(const Config& cfg, int64_t nrow, int64_t ncol) {
   const char* e = tuning::Get(tuning::Knob::DeviceBinning);
@@ -238,6 +244,7 @@ std::vector<char> DeviceBinDenseMatrix(Dataset* ds, const void* data, bool is_f6
     }
   }
   for (const auto& F : feats) done_col[F.col] = 1;
+  NoteDeviceBinCall(false);
   return done_col;
 }
 

@@ -459,6 +459,7 @@ void FeatureGroup::MergePushes() {
   std::vector<std::pair<data_size_t, uint32_t>> all;
   size_t total = sp_rows.size();
   for (const auto& b : push_buf) total += b.size();
+  if (total == sp_rows.size()) return;  // (nothing pushed: the stored rows stay as they are)
   all.reserve(total);
   for (size_t k = 0; k < sp_rows.size(); ++k) all.emplace_back(sp_rows[k], ValAt(k));  // (earlier merges)
   for (auto& b : push_buf) {
@@ -618,6 +619,24 @@ void Dataset::PushSparseRow(data_size_t row, const std::vector<std::pair<int, do
   }
   for (int inner : need_push_zeros_) {
     if (!added[inner]) PushColumnValue(row, real_feature_idx_[inner], 0.0);
+  }
+}
+
+void Dataset::PushSparseRowOfGroups(data_size_t row, const std::vector<std::pair<int, double>>& values,
+                                    const std::vector<char>& done_group) {
+  bool zeros = false;
+  for (int inner : need_push_zeros_) zeros = zeros || !done_group[feature2group_[inner]];
+  std::vector<char> added(zeros ? num_features_ : 0, 0);
+  for (auto& kv : values) {
+    if (kv.first >= num_total_features_) continue;
+    const int inner = used_feature_map_[kv.first];
+    if (inner < 0 || done_group[feature2group_[inner]]) continue;
+    if (zeros) added[inner] = 1;
+    PushColumnValue(row, kv.first, kv.second);
+  }
+  if (!zeros) return;
+  for (int inner : need_push_zeros_) {
+    if (!done_group[feature2group_[inner]] && !added[inner]) PushColumnValue(row, real_feature_idx_[inner], 0.0);
   }
 }
 
