@@ -310,6 +310,23 @@ LIGHTGBM_C_EXPORT int LGBM_AMD_CsrBinLaunchInfo(int64_t* out);
 // matrices this process has binned on the device: dense (LGBM_DatasetCreateFromMat) and CSR
 // (LGBM_DatasetCreateFromCSR); tests: whether a construction took the device path
 LIGHTGBM_C_EXPORT int LGBM_AMD_DeviceBinStats(int64_t* dense_calls, int64_t* csr_calls);
+// the rule of the device binning of a CSC matrix (src/device/csc_bins.h) evaluated on the host
+// with a constructed dataset's bin mappers (no GPU): bins is row-major [num_row][*num_groups], the
+// layout of LGBM_AMD_CsrToGroupBins.  Entries on a row outside [0, num_row), on a column not below
+// the dataset's num_total_features or on an unused feature are dropped; col_ptr (ncol_ptr entries)
+// is clamped to [0, nelem].  With bins or col_ptr null only *num_groups is returned
+LIGHTGBM_C_EXPORT int LGBM_AMD_CscToGroupBins(DatasetHandle handle, const void* col_ptr, int col_ptr_type,
+                                              const int32_t* indices, const void* data, int data_type,
+                                              int64_t ncol_ptr, int64_t nelem, int64_t num_row, int32_t* bins,
+                                              int* num_groups);
+// the launch shape of the CSC binning (src/device/csc_bin_kernels.hip; tests place columns on its
+// boundaries): out[0] the stored entries of a column that one wave takes, out[1] the most features
+// whose zeros are pushed, out[2] the rows of a compaction tile, out[3] the threads of a workgroup,
+// out[4] the entries the single wave of an unsorted column reads at a time
+LIGHTGBM_C_EXPORT int LGBM_AMD_CscBinLaunchInfo(int64_t* out);
+// CSC matrices this process has binned on the device (LGBM_DatasetCreateFromCSC), and bin samples
+// it has taken column by column; tests: whether a construction took the device path
+LIGHTGBM_C_EXPORT int LGBM_AMD_DeviceBinCscStats(int64_t* csc_calls, int64_t* column_samples);
 // predictions this process has computed on the device, over all boosters (tests: whether a call
 // took the device path or the host predictor)
 LIGHTGBM_C_EXPORT int LGBM_AMD_DevicePredictCount(int64_t* out);

@@ -79,6 +79,8 @@ constexpr int kQueryMetricDeviceMaxDocs = 16384;
   X(TextBlockBytes, "LGBM_AMD_TEXT_BLOCK_BYTES", "n: text reader block size (tests)")                          \
   X(PredictChunkRows, "LGBM_AMD_PREDICT_CHUNK_ROWS", "n: rows per chunk of a device prediction (tests; auto from free memory)")  \
   X(BinChunkRows, "LGBM_AMD_BIN_CHUNK_ROWS", "n: rows per chunk of the device binning of a CSR matrix (tests; auto: 256 MiB of entries / of bins)")  \
+  X(BinChunkGroups, "LGBM_AMD_BIN_CHUNK_GROUPS", "n: feature groups per window of the device binning of a CSC matrix (tests; auto: 256 MiB of bins and entries)")  \
+  X(CscColumnSample, "LGBM_AMD_CSC_COLUMN_SAMPLE", "1: the host CSC construction takes its bin sample column by column, as the device path does (tests, A/B; same dataset)")  \
   X(RefitWindow, "LGBM_AMD_REFIT_WINDOW", "n: iterations per staged window of a device refit (tests; auto from free memory)")  \
   X(RefitWide, "LGBM_AMD_REFIT_WIDE", "1: a device refit stages leaf ids as int32 (tests; auto above 65536 leaves)")  \
   /* tuning (same models; defaults above) */                                                                   \

@@ -27,6 +27,9 @@ the kernels can be checked one by one against plain PyTorch references
   by the kernel that bins a scipy CSR matrix when a Dataset is constructed with
   ``device_type=gpu`` (src/device/csr_bin_kernels.hip; reference Dataset::PushOneRow);
   :func:`csr_bin_launch_info` gives its launch shape
+* :func:`csc_group_bins` -- the same matrix from the columns of a CSC matrix, by the kernels that
+  bin a scipy CSC matrix (src/device/csc_bin_kernels.hip); :func:`csc_bin_launch_info` gives
+  their launch shape
 
 There is no host fallback: the ops need a GPU and the in-tree library.
 """
@@ -311,6 +314,48 @@ def csr_group_bins(dataset, X):
             _dev_ptr(col, torch.int32, "col_indices"), _dev_ptr(values, X.dtype, "values"),
             ctypes.c_int(0 if X.dtype == torch.float32 else 1), ctypes.c_int64(n), ctypes.c_int64(values.numel()),
             _dev_ptr(out, torch.int32, "out")))
+    return out
+
+
+def csc_bin_launch_info():
+    """The launch shape of the CSC binning kernels (src/device/csc_bin_kernels.hip):
+    ``segment_entries`` (the stored entries of a column that one wave takes),
+    ``max_push_zero_features`` (with more features whose default bin is not their most frequent bin
+    a matrix is binned on the host), ``tile_rows`` (rows per tile of the compaction of sparse groups
+    and of the pass that pushes zeros), ``block`` (threads of a workgroup) and ``batch`` (the entries
+    the single wave of a column with repeated or unsorted rows reads at a time)."""
+    out = (ctypes.c_int64 * 5)()
+    _native_call("LGBM_AMD_CscBinLaunchInfo", out)
+    return {"segment_entries": out[0], "max_push_zero_features": out[1], "tile_rows": out[2], "block": out[3],
+            "batch": out[4]}
+
+
+def csc_group_bins(dataset, X):
+    """The group bins of the rows of ``X``, a ``torch.sparse_csc`` GPU tensor with float32 or float64
+    values (int32 or int64 ``ccol_indices``; int64 ``row_indices`` are converted to int32 on the
+    device), under the bin mappers of the constructed ``dataset``: the matrix of
+    :func:`csr_group_bins`.  Entries on rows outside the matrix or on columns the dataset does not
+    have are dropped, and of several writes to one cell the one stored last wins."""
+    torch = _torch()
+    if not isinstance(X, torch.Tensor) or X.layout != torch.sparse_csc or X.dim() != 2 or \
+            X.dtype not in (torch.float32, torch.float64):
+        raise LightGBMError("X must be a 2-d float32 or float64 torch.sparse_csc tensor on the GPU")
+    handle = dataset.construct().handle
+    ccol, values = X.ccol_indices().contiguous(), X.values().contiguous()
+    if ccol.dtype not in (torch.int32, torch.int64):
+        raise LightGBMError("ccol_indices must be int32 or int64")
+    row = X.row_indices().to(torch.int32).contiguous()
+    ng = ctypes.c_int(0)
+    _native_call("LGBM_AMD_DatasetGetGroupBins", handle, None, None, ctypes.byref(ng))
+    n = X.shape[0]
+    out = torch.empty((n, ng.value), dtype=torch.int32, device=X.device)
+    torch.cuda.synchronize(X.device)
+    with torch.cuda.device(X.device):
+        _check(_lib().LGBMAMD_OpCscGroupBins(
+            handle, _dev_ptr(ccol, ccol.dtype, "ccol_indices"), ctypes.c_int(2 if ccol.dtype == torch.int32 else 3),
+            _dev_ptr(row, torch.int32, "row_indices"), _dev_ptr(values, X.dtype, "values"),
+            ctypes.c_int(0 if X.dtype == torch.float32 else 1), ctypes.c_int64(ccol.numel()),
+            ctypes.c_int64(values.numel()), ctypes.c_int64(n), _dev_ptr(out, torch.int32, "out")))
     return out
 
 

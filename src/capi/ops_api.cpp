@@ -8,7 +8,8 @@
 // tests/test_rank_ops.py); a booster's forest prediction (scores, leaf indices, SHAP
 // contributions) on a matrix that already is on the device; and the two per-tree passes of a
 // device refit (src/device/refit_kernels.hip: per-leaf sums, score update; tests/test_device_refit.py);
-// and the CSR binning kernel under a dataset's bin mappers (src/device/csr_bin_kernels.hip).
+// and the CSR / CSC binning kernels under a dataset's bin mappers (src/device/csr_bin_kernels.hip,
+// src/device/csc_bin_kernels.hip).
 //
 // Objectives and metrics are created from a parameter string exactly as training creates
 // them (reference objective_function.cpp:16-56, metric.cpp:16-63), so the kernels see the
@@ -215,6 +216,19 @@ LIGHTGBM_C_EXPORT int LGBMAMD_OpCsrGroupBins(DatasetHandle handle, const void* d
   return Guard([&] {
     CsrGroupBinsOnDevice(*static_cast<const Dataset*>(handle), d_indptr, indptr_type, d_indices, d_data, data_type,
                          nrow, nelem, d_bins);
+  });
+}
+
+// ... and of the num_row rows of a CSC matrix in device memory (d_col_ptr: ncol_ptr int32 / int64
+// entries; d_indices: the int32 row of each of the nelem entries), by the kernels of
+// LGBM_DatasetCreateFromCSC's device path (src/device/csc_bin_kernels.hip) -- the matrix of
+// LGBM_AMD_CscToGroupBins
+LIGHTGBM_C_EXPORT int LGBMAMD_OpCscGroupBins(DatasetHandle handle, const void* d_col_ptr, int col_ptr_type,
+                                             const int32_t* d_indices, const void* d_data, int data_type,
+                                             int64_t ncol_ptr, int64_t nelem, int64_t num_row, int32_t* d_bins) {
+  return Guard([&] {
+    CscGroupBinsOnDevice(*static_cast<const Dataset*>(handle), d_col_ptr, col_ptr_type, d_indices, d_data, data_type,
+                         ncol_ptr, nelem, num_row, d_bins);
   });
 }
 

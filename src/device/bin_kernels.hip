@@ -120,6 +120,14 @@ bool UseDeviceBinningCsr(const Config& cfg, int64_t nelem) {
   return BinningDevice(cfg) >= 0;
 }
 
+bool UseDeviceBinningCsc(const Config& cfg, int64_t nelem) {
+  const char* e = tuning::Get(tuning::Knob::DeviceBinning);
+  if (e != nullptr && e[0] == '0') return false;
+  const bool forced = e != nullptr && e[0] == '1';
+  if (!forced && (cfg.device_type != "gpu" || nelem < kCscBinMinEntries)) return false;
+  return BinningDevice(cfg) >= 0;
+}
+
 bool UseDeviceBinning(const Config& cfg, int64_t nrow, int64_t ncol) {
   const char* e = tuning::Get(tuning::Knob::DeviceBinning);
   if (e != nullptr && e[0] == '0') return false;

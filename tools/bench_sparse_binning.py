@@ -13,10 +13,21 @@ path, so the host clock around it covers the device work.  Host and device alter
 run after a warm-up of each; the median of --repeats is reported.  "equal" tells whether both
 paths saved the same binary file (checked on the smallest sweep entry).  Prints one JSON line.
 
+--layout csc times LGBM_DatasetCreateFromCSC on the same matrices converted to CSC, on three paths:
+  host     LGBM_AMD_DEVICE_BINNING=0: the matrix transposed into rows, every row pushed
+  tocsr    X.tocsr() inside the timed region, then the device CSR path
+  device   the device CSC path (src/device/csc_bin_kernels.hip)
+--equal-full compares the binary files of all paths at every full shape as well; --shuffle-column
+times the device CSC path again with the entries of one column in shuffled order (that column is
+walked by a single wave).
+
   python tools/bench_sparse_binning.py
   python tools/bench_sparse_binning.py --shapes 200000x2000x40 --sweep
   rocprofv3 --kernel-trace --stats -- python tools/bench_sparse_binning.py --shapes 1000000x2000x40 \\
       --sweep --modes 1 --repeats 1       # (the kernels of the device path alone)
+  python tools/bench_sparse_binning.py --layout csc --equal-full --shuffle-column
+  rocprofv3 --kernel-trace --stats -- python tools/bench_sparse_binning.py --layout csc --sweep \
+      --paths device --repeats 1
 """
 import argparse
 import ctypes
@@ -53,6 +64,23 @@ def csr_calls():
     return out.value
 
 
+def csc_calls():
+    from lightgbmv1_amd import _native as nat
+    out = ctypes.c_int64(0)
+    nat.call("LGBM_AMD_DeviceBinCscStats", ctypes.byref(out), None)
+    return out.value
+
+
+def shuffled_column(X):
+    """a copy of the CSC matrix X with the entries of its longest column in shuffled order"""
+    c = int(np.argmax(np.diff(X.indptr)))
+    s, e = X.indptr[c], X.indptr[c + 1]
+    order = np.random.RandomState(3).permutation(e - s)
+    indices, data = X.indices.copy(), X.data.copy()
+    indices[s:e], data[s:e] = indices[s:e][order], data[s:e][order]
+    return sp.csc_matrix((data, indices, X.indptr), shape=X.shape)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--shapes", nargs="*", default=["1000000x2000x40", "10000000x40x4"])
@@ -61,6 +89,10 @@ def main():
     ap.add_argument("--modes", nargs="*", default=["0", "1"], choices=["0", "1"])
     ap.add_argument("--repeats", type=int, default=3)
     ap.add_argument("--host-threads", type=int, default=16)
+    ap.add_argument("--layout", default="csr", choices=["csr", "csc"])
+    ap.add_argument("--paths", nargs="*", default=None, help="only these paths (host, tocsr, device)")
+    ap.add_argument("--equal-full", action="store_true", help="compare the files at the full shapes too")
+    ap.add_argument("--shuffle-column", action="store_true", help="csc: one column unsorted, device path")
     args = ap.parse_args()
 
     import lightgbmv1_amd as lgb
@@ -70,55 +102,87 @@ def main():
     params = {"objective": "regression", "device_type": "gpu", "max_bin": 255, "verbose": -1,
               "num_threads": args.host_threads}
 
-    def build(X, mode, reference=None):
+    csc = args.layout == "csc"
+    # the paths timed: (name, LGBM_AMD_DEVICE_BINNING, convert to CSR inside the timed region)
+    if csc:
+        paths = [("host", "0", False), ("tocsr", "1", True), ("device", "1", False)]
+    else:
+        paths = [("host", "0", False), ("device", "1", False)]
+    paths = [p for p in paths if p[1] in args.modes and (args.paths is None or p[0] in args.paths)]
+
+    def build(X, path, reference=None):
+        name, mode, convert = path
         os.environ["LGBM_AMD_DEVICE_BINNING"] = mode
-        before = csr_calls()
+        before = csr_calls(), csc_calls()
         t = time.perf_counter()
-        ds = lgb.Dataset(X, params=params if reference is None else None, reference=reference).construct()
+        ds = lgb.Dataset(X.tocsr() if convert else X, params=params if reference is None else None,
+                         reference=reference).construct()
         dt = time.perf_counter() - t
-        if (csr_calls() != before) != (mode == "1"):
-            raise SystemExit("LGBM_AMD_DEVICE_BINNING=%s did not choose the path" % mode)
+        took = csr_calls() != before[0], csc_calls() != before[1]
+        if took != (mode == "1" and (convert or not csc), mode == "1" and csc and not convert):
+            raise SystemExit("path %s did not run as asked" % name)
         return dt, ds
 
-    def measure(X):
+    def measure(X, paths=paths, note=None):
         out = {"rows": X.shape[0], "cols": X.shape[1], "entries": int(X.nnz)}
-        times = {(m, k): [] for m in args.modes for k in ("train", "valid")}
-        for rep in range(args.repeats + 1):  # (the first round warms both paths up)
-            for mode in args.modes:
-                dt, train = build(X, mode)
-                dv, valid = build(X, mode, reference=train)
+        if note:
+            out["note"] = note
+        times = {(p[0], k): [] for p in paths for k in ("train", "valid")}
+        for rep in range(args.repeats + 1):  # (the first round warms every path up)
+            for path in paths:
+                dt, train = build(X, path)
+                dv, valid = build(X, path, reference=train)
                 if rep > 0:
-                    times[(mode, "train")].append(dt)
-                    times[(mode, "valid")].append(dv)
+                    times[(path[0], "train")].append(dt)
+                    times[(path[0], "valid")].append(dv)
                 del train, valid
-        for (mode, kind), v in times.items():
-            out["%s_%s_s" % ("host" if mode == "0" else "device", kind)] = round(statistics.median(v), 4)
+        for (name, kind), v in times.items():
+            out["%s_%s_s" % (name, kind)] = round(statistics.median(v), 4)
+            out["%s_%s_all" % (name, kind)] = [round(x, 4) for x in v]
         print(json.dumps(out), file=sys.stderr, flush=True)  # (progress; the result line goes to stdout)
         return out
 
-    result = {"tool": "bench_sparse_binning", "host_threads": args.host_threads, "repeats": args.repeats,
-              "shapes": [], "sweep": []}
+    def files_equal(X):
+        """whether every path saves the same training set and the same reference= set of its first third"""
+        files = []
+        with tempfile.TemporaryDirectory() as d:
+            for path in paths:
+                _, train = build(X, path)
+                _, valid = build(X[:max(1, X.shape[0] // 3)], path, reference=train)
+                mine = []
+                for k, ds in enumerate((train, valid)):
+                    f = os.path.join(d, "%s_%d.bin" % (path[0], k))
+                    ds.save_binary(f)
+                    with open(f, "rb") as fh:
+                        mine.append(fh.read())
+                    os.remove(f)
+                files.append(mine)
+                del train, valid
+        return all(f == files[0] for f in files[1:])
+
+    result = {"tool": "bench_sparse_binning", "layout": args.layout, "host_threads": args.host_threads,
+              "repeats": args.repeats, "shapes": [], "sweep": []}
     first = None
     for k, shape in enumerate(args.shapes):
         rows, cols, per_row = (int(v) for v in shape.split("x"))
         X = make_csr(rows, cols, per_row, 1 + k)
         if first is None:
-            first = X
+            first = X  # (CSR: the sweep slices rows)
+        if csc:
+            X = X.tocsc()
         result["shapes"].append(measure(X))
+        if args.equal_full and len(paths) > 1:
+            result["shapes"][-1]["equal"] = files_equal(X)
+        if csc and args.shuffle_column:
+            device = [p for p in paths if p[0] == "device"]
+            result["shapes"].append(measure(shuffled_column(X), device, "one column shuffled"))
         del X
     for rows in args.sweep:
         if first is not None and rows < first.shape[0]:
-            result["sweep"].append(measure(first[:rows]))
-    if first is not None and len(args.modes) == 2:
+            result["sweep"].append(measure(first[:rows].tocsc() if csc else first[:rows]))
+    if first is not None and len(paths) > 1:
         small = first[:min([first.shape[0]] + [r for r in args.sweep if r < first.shape[0]])]
-        files = []
-        with tempfile.TemporaryDirectory() as d:
-            for mode in ("0", "1"):
-                _, ds = build(small, mode)
-                ds.save_binary(os.path.join(d, mode + ".bin"))
-                with open(os.path.join(d, mode + ".bin"), "rb") as f:
-                    files.append(f.read())
-        result["equal"] = files[0] == files[1]
+        result["equal"] = files_equal(small.tocsc() if csc else small)
     print(json.dumps(result))
 
 
