@@ -21,6 +21,7 @@
 
 #include <atomic>
 #include <cstring>
+#include <type_traits>
 #include <vector>
 
 #include "../device/csc_slots.h"
@@ -29,6 +30,7 @@
 #include "shap_paths.h"
 #include "lgbm_amd/boosting.h"
 #include "lgbm_amd/log.h"
+#include "lgbm_amd/sparse_ptr.h"
 #include "lgbm_amd/tuning.h"
 
 namespace lgbm_amd {
@@ -285,10 +287,6 @@ void GBDT::PredictDeviceBuffers(const void* d_data, bool is_double, int64_t nrow
 
 namespace {
 
-int64_t PtrAt(const void* indptr, bool is_64, int64_t i) {
-  return is_64 ? static_cast<const int64_t*>(indptr)[i] : static_cast<int64_t>(static_cast<const int32_t*>(indptr)[i]);
-}
-
 // the scatter of CSR rows [0, rows) (indptr on the device, entry_base = its first value) into d_mat
 void RunCsrToSlots(const DeviceForest& forest, const void* d_indptr, bool indptr_is_64, const int32_t* d_indices,
                    const void* d_data, bool is_double, int64_t rows, int64_t entry_base, int64_t entries,
@@ -322,10 +320,8 @@ bool GBDT::PredictCSROnDevice(const void* indptr, bool indptr_is_64, const int32
   if (num_tree_per_iteration_ > dev::kMaxPredClasses || nrow <= 0) return false;
   // (rows are copied by their indptr entries: a matrix whose indptr does not ascend within the
   // stored entries is left to the host)
-  if (PtrAt(indptr, indptr_is_64, 0) < 0 || PtrAt(indptr, indptr_is_64, nrow) > nelem) return false;
-  for (int64_t r = 0; r < nrow; ++r) {
-    if (PtrAt(indptr, indptr_is_64, r) > PtrAt(indptr, indptr_is_64, r + 1)) return false;
-  }
+  const SparsePtr ptr{indptr, indptr_is_64};
+  if (!PointerValid(ptr, nrow, nelem)) return false;
   const int ntpi = num_tree_per_iteration_;
   const int num_features = max_feature_idx_ + 1;
   const std::vector<const Tree*> trees = PredictWindowTrees(start_iteration, num_iteration);
@@ -356,7 +352,7 @@ bool GBDT::PredictCSROnDevice(const void* indptr, bool indptr_is_64, const int32
       auto most_entries = [&](int64_t rows) {
         int64_t most = 0;
         for (int64_t r0 = 0; r0 < nrow; r0 += rows) {
-          most = std::max(most, PtrAt(indptr, indptr_is_64, std::min(r0 + rows, nrow)) - PtrAt(indptr, indptr_is_64, r0));
+          most = std::max(most, ptr[std::min(r0 + rows, nrow)] - ptr[r0]);
         }
         return most;
       };
@@ -382,8 +378,8 @@ bool GBDT::PredictCSROnDevice(const void* indptr, bool indptr_is_64, const int32
         double* host_out = convert ? raw_out.data() : out;
         for (int64_t r0 = 0; r0 < nrow; r0 += chunk) {
           const int64_t rows = std::min(chunk, nrow - r0);
-          const int64_t e0 = PtrAt(indptr, indptr_is_64, r0);
-          const int64_t ne = PtrAt(indptr, indptr_is_64, r0 + rows) - e0;
+          const int64_t e0 = ptr[r0];
+          const int64_t ne = ptr[r0 + rows] - e0;
           HIPCHECK(hipMemcpyAsync(d_indptr, static_cast<const char*>(indptr) + static_cast<size_t>(r0) * ptr_b,
                                   static_cast<size_t>(rows + 1) * ptr_b, hipMemcpyHostToDevice, s));
           if (ne > 0) {
@@ -465,13 +461,10 @@ void GBDT::CsrToSlotsOnHost(const void* indptr, bool indptr_is_64, const int32_t
   if (matrix == nullptr || nindptr <= 1) return;
   const int64_t rows = nindptr - 1;
   const int32_t* so = slots.slot_of.data();
-  if (is_double) {
-    if (indptr_is_64) dev::EvalCsrToSlots(static_cast<const int64_t*>(indptr), 0, indices, static_cast<const double*>(data), rows, nelem, so, nf, ns, static_cast<double*>(matrix));
-    else dev::EvalCsrToSlots(static_cast<const int32_t*>(indptr), 0, indices, static_cast<const double*>(data), rows, nelem, so, nf, ns, static_cast<double*>(matrix));
-  } else {
-    if (indptr_is_64) dev::EvalCsrToSlots(static_cast<const int64_t*>(indptr), 0, indices, static_cast<const float*>(data), rows, nelem, so, nf, ns, static_cast<float*>(matrix));
-    else dev::EvalCsrToSlots(static_cast<const int32_t*>(indptr), 0, indices, static_cast<const float*>(data), rows, nelem, so, nf, ns, static_cast<float*>(matrix));
-  }
+  DispatchSparse(indptr_is_64, is_double, indptr, data, [&](auto* ptr, auto* val) {
+    using T = std::decay_t<decltype(*val)>;
+    dev::EvalCsrToSlots(ptr, 0, indices, val, rows, nelem, so, nf, ns, static_cast<T*>(matrix));
+  });
 }
 
 namespace {
@@ -518,10 +511,7 @@ bool GBDT::PredictCSCOnDevice(const void* col_ptr, bool col_ptr_is_64, const int
   if (num_tree_per_iteration_ > dev::kMaxPredClasses || num_row <= 0 || ncol < 0 || nelem < 0) return false;
   // (columns are copied by their pointer entries: a matrix whose pointer does not ascend within
   // the stored entries is left to the host)
-  if (PtrAt(col_ptr, col_ptr_is_64, 0) < 0 || PtrAt(col_ptr, col_ptr_is_64, ncol) > nelem) return false;
-  for (int64_t c = 0; c < ncol; ++c) {
-    if (PtrAt(col_ptr, col_ptr_is_64, c) > PtrAt(col_ptr, col_ptr_is_64, c + 1)) return false;
-  }
+  if (!PointerValid(SparsePtr{col_ptr, col_ptr_is_64}, ncol, nelem)) return false;
   const int ntpi = num_tree_per_iteration_;
   const int num_features = max_feature_idx_ + 1;
   const std::vector<const Tree*> trees = PredictWindowTrees(start_iteration, num_iteration);
@@ -536,22 +526,12 @@ bool GBDT::PredictCSCOnDevice(const void* col_ptr, bool col_ptr_is_64, const int
       const int64_t per_out = forest.OutPerRow();
       // the stored entries of the used columns, packed slot after slot: a pointer of nslot + 1
       // entries over them, and the runs of adjacent used columns, each one copy
-      struct Run {
-        int64_t src, dst, len;
-      };
-      std::vector<int64_t> ptr(static_cast<size_t>(nslot) + 1, 0);
+      std::vector<int64_t> ptr;
+      std::vector<ColumnRun> runs;
+      PackColumnRuns(forest.Used(), SparsePtr{col_ptr, col_ptr_is_64}, ncol, &runs, &ptr);
       std::vector<int32_t> slot_col(nslot, -1);
-      std::vector<Run> runs;
       for (int k = 0; k < nslot; ++k) {
-        const int64_t f = forest.Used()[k];
-        ptr[k + 1] = ptr[k];
-        if (f >= ncol) continue;  // (a matrix narrower than the model: the feature reads 0)
-        slot_col[k] = k;
-        const int64_t a = PtrAt(col_ptr, col_ptr_is_64, f), b = PtrAt(col_ptr, col_ptr_is_64, f + 1);
-        ptr[k + 1] = ptr[k] + (b - a);
-        if (b == a) continue;
-        if (!runs.empty() && runs.back().src + runs.back().len == a) runs.back().len += b - a;
-        else runs.push_back({a, ptr[k], b - a});
+        if (forest.Used()[k] < ncol) slot_col[k] = k;  // (else a matrix narrower than the model: it reads 0)
       }
       const int64_t entries = ptr[nslot];
       // rows per chunk: the compact matrix, the output and the accumulator tiles within most of
@@ -577,7 +557,7 @@ bool GBDT::PredictCSCOnDevice(const void* col_ptr, bool col_ptr_is_64, const int
         uint32_t* d_ascending = static_cast<uint32_t*>(b.Alloc(static_cast<size_t>(nslot) * sizeof(uint32_t)));
         // (every run where it lies: packing the runs on the host first, for two large copies, was
         // measured slower at 266 runs -- profiles/r12_device_csc_predict.md)
-        for (const Run& r : runs) {
+        for (const ColumnRun& r : runs) {
           HIPCHECK(hipMemcpyAsync(d_indices + r.dst, indices + r.src, static_cast<size_t>(r.len) * sizeof(int32_t),
                                   hipMemcpyHostToDevice, s));
           HIPCHECK(hipMemcpyAsync(d_data + static_cast<size_t>(r.dst) * elem,
@@ -682,13 +662,10 @@ void GBDT::CscToSlotsOnHost(const void* col_ptr, bool col_ptr_is_64, const int32
     if (slots.used[k] < ncol_ptr - 1) slot_col[k] = slots.used[k];
   }
   const int32_t* sc = slot_col.data();
-  if (is_double) {
-    if (col_ptr_is_64) dev::EvalCscToSlots(static_cast<const int64_t*>(col_ptr), sc, indices, static_cast<const double*>(data), nelem, row0, rows, ns, static_cast<double*>(matrix));
-    else dev::EvalCscToSlots(static_cast<const int32_t*>(col_ptr), sc, indices, static_cast<const double*>(data), nelem, row0, rows, ns, static_cast<double*>(matrix));
-  } else {
-    if (col_ptr_is_64) dev::EvalCscToSlots(static_cast<const int64_t*>(col_ptr), sc, indices, static_cast<const float*>(data), nelem, row0, rows, ns, static_cast<float*>(matrix));
-    else dev::EvalCscToSlots(static_cast<const int32_t*>(col_ptr), sc, indices, static_cast<const float*>(data), nelem, row0, rows, ns, static_cast<float*>(matrix));
-  }
+  DispatchSparse(col_ptr_is_64, is_double, col_ptr, data, [&](auto* ptr, auto* val) {
+    using T = std::decay_t<decltype(*val)>;
+    dev::EvalCscToSlots(ptr, sc, indices, val, nelem, row0, rows, ns, static_cast<T*>(matrix));
+  });
 }
 
 int64_t GBDT::DevicePredictions() { return g_device_predictions.load(); }

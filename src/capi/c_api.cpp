@@ -33,6 +33,7 @@
 #include "lgbm_amd/objective.h"
 #include "lgbm_amd/predictor.h"
 #include "lgbm_amd/random.h"
+#include "lgbm_amd/sparse_ptr.h"
 #include "lgbm_amd/tuning.h"
 #include "../device/csc_bins.h"
 #include "../device/kernels.h"
@@ -144,15 +145,12 @@ std::function<Row(int64_t)> CSRRowFun(const void* indptr, int indptr_type, const
                                       int dtype, int64_t nindptr, int64_t nelem) {
   (void)nindptr;
   (void)nelem;
-  auto ptr_at = [=](int64_t i) -> int64_t {
-    return indptr_type == C_API_DTYPE_INT32 ? static_cast<const int32_t*>(indptr)[i]
-                                            : static_cast<const int64_t*>(indptr)[i];
-  };
+  const SparsePtr ptr{indptr, indptr_type != C_API_DTYPE_INT32};
   if (indptr_type != C_API_DTYPE_INT32 && indptr_type != C_API_DTYPE_INT64) Log::Fatal("Unknown indptr type");
   if (dtype != C_API_DTYPE_FLOAT32 && dtype != C_API_DTYPE_FLOAT64) Log::Fatal("Unknown data type in CSR");
   return [=](int64_t r) {
     Row out;
-    const int64_t s = ptr_at(r), e = ptr_at(r + 1);
+    const int64_t s = ptr[r], e = ptr[r + 1];
     out.reserve(e - s);
     for (int64_t i = s; i < e; ++i) {
       out.emplace_back(indices[i], dtype == C_API_DTYPE_FLOAT32 ? ValAt<float>(data, i) : ValAt<double>(data, i));
@@ -165,12 +163,9 @@ std::function<Row(int64_t)> CSRRowFun(const void* indptr, int indptr_type, const
 std::vector<Row> CSCToRows(const void* col_ptr, int col_ptr_type, const int32_t* indices, const void* data,
                            int dtype, int64_t ncol_ptr, int64_t num_row) {
   std::vector<Row> rows(num_row);
-  auto ptr_at = [=](int64_t i) -> int64_t {
-    return col_ptr_type == C_API_DTYPE_INT32 ? static_cast<const int32_t*>(col_ptr)[i]
-                                             : static_cast<const int64_t*>(col_ptr)[i];
-  };
+  const SparsePtr ptr{col_ptr, col_ptr_type != C_API_DTYPE_INT32};
   for (int64_t c = 0; c + 1 < ncol_ptr; ++c) {
-    for (int64_t i = ptr_at(c); i < ptr_at(c + 1); ++i) {
+    for (int64_t i = ptr[c]; i < ptr[c + 1]; ++i) {
       const double v = dtype == C_API_DTYPE_FLOAT32 ? ValAt<float>(data, i) : ValAt<double>(data, i);
       rows[indices[i]].emplace_back(static_cast<int>(c), v);
     }
@@ -253,12 +248,9 @@ Dataset* DatasetFromRows(const std::function<Row(int64_t)>& get_row, data_size_t
 std::vector<Row> CSCColumnsToRows(const void* col_ptr, int col_ptr_type, const int32_t* indices, const void* data,
                                   int dtype, const std::vector<int>& cols, int64_t num_row) {
   std::vector<Row> rows(num_row);
-  auto ptr_at = [=](int64_t i) -> int64_t {
-    return col_ptr_type == C_API_DTYPE_INT32 ? static_cast<const int32_t*>(col_ptr)[i]
-                                             : static_cast<const int64_t*>(col_ptr)[i];
-  };
+  const SparsePtr ptr{col_ptr, col_ptr_type != C_API_DTYPE_INT32};
   for (int c : cols) {
-    for (int64_t i = ptr_at(c); i < ptr_at(c + 1); ++i) {
+    for (int64_t i = ptr[c]; i < ptr[c + 1]; ++i) {
       if (indices[i] < 0 || indices[i] >= num_row) continue;
       const double v = dtype == C_API_DTYPE_FLOAT32 ? ValAt<float>(data, i) : ValAt<double>(data, i);
       rows[indices[i]].emplace_back(c, v);
@@ -291,16 +283,11 @@ Dataset* DatasetFromCSCColumns(const void* col_ptr, int col_ptr_type, const int3
 #pragma omp parallel for schedule(dynamic, 16)
     for (int c = 0; c < ncol; ++c) {
       errors.Run([&] {
-        auto run = [&](auto* ptr, auto* val) {
-          dev::CscColumnSample(ptr, c, indices, val, nelem, pos.data(), num_row, kZeroThreshold, &sv[c], &si[c]);
-        };
-        if (col_ptr_type == C_API_DTYPE_INT64) {
-          if (dtype == C_API_DTYPE_FLOAT64) run(static_cast<const int64_t*>(col_ptr), static_cast<const double*>(data));
-          else run(static_cast<const int64_t*>(col_ptr), static_cast<const float*>(data));
-        } else {
-          if (dtype == C_API_DTYPE_FLOAT64) run(static_cast<const int32_t*>(col_ptr), static_cast<const double*>(data));
-          else run(static_cast<const int32_t*>(col_ptr), static_cast<const float*>(data));
-        }
+        DispatchSparse(col_ptr_type == C_API_DTYPE_INT64, dtype == C_API_DTYPE_FLOAT64, col_ptr, data,
+                       [&](auto* ptr, auto* val) {
+                         dev::CscColumnSample(ptr, c, indices, val, nelem, pos.data(), num_row, kZeroThreshold, &sv[c],
+                                              &si[c]);
+                       });
       });
     }
     errors.Check();

@@ -5,21 +5,16 @@
 // per eligible group, [group][row] at the group's bin_bytes, here over all rows of the matrix and
 // the groups of one window.  A feature's values are one contiguous run of stored entries.
 //
-//   k_csc_bin_column_order  one flag per column of the window: its row indices ascend strictly
-//                        (what scipy and torch build), so no cell is stored twice.
-//   k_csc_to_group_bins  a column is cut into segments of kCscBinSegmentEntries entries, one wave
-//                        each (wave w of the column's waves takes segments w, w + waves, ...), lanes
+//   k_csc_bin_column_order  one flag per column of the window: its row indices ascend strictly.
+//   k_csc_to_group_bins  a column is walked as src/device/stored_order.h says (WalkColumn), lanes
 //                        on consecutive entries: the row, the value's bin by binary search over the
 //                        upper bounds in global memory, the group cell, a store into the group's
-//                        column.  A column without the flag is walked by one wave alone in stored
-//                        order, 64 entries at a time: of a batch's lanes writing one row only the
-//                        highest stores (ballots) and between batches the wave waits for its
-//                        stores, as in k_csr_to_group_bins.  Launch m takes the m-th member, by
-//                        ascending column, of every group of the window, and the stream orders the
-//                        launches: a higher column of a bundle overwrites a lower one, no two
-//                        waves of a launch store to one cell, and the result is the same on every
-//                        run.  Entries of a feature whose zeros are pushed set their row's bit in
-//                        the feature's bitset of named rows (atomicOr: the order does not matter).
+//                        column.  Launch m takes the m-th member, by ascending column, of every
+//                        group of the window, and the stream orders the launches: a higher column
+//                        of a bundle overwrites a lower one, no two waves of a launch store to one
+//                        cell, and the result is the same on every run.  Entries of a feature whose
+//                        zeros are pushed set their row's bit in the feature's bitset of named rows
+//                        (atomicOr: the order does not matter).
 //   k_csc_push_zeros     one thread per (row, group with such features): the features in push
 //                        order, the last one whose bit is clear stores its bin of 0.0.
 // Sparse groups are compacted and dense groups copied back as on the CSR path.  Windows are made
@@ -38,17 +33,16 @@
 #include "csc_bins.h"
 #include "group_bin_scratch.h"
 #include "lgbm_amd/device_binning.h"
+#include "lgbm_amd/sparse_ptr.h"
 #include "lgbm_amd/tuning.h"
 
 namespace lgbm_amd {
 
 namespace {
 
-constexpr int kCscBinThreads = 256;
-constexpr int kCscBinWaves = kCscBinThreads / kWave;
-constexpr int kCscBinSegmentEntries = 512;
-constexpr int kCscBinGridBlocks = 8192;  // workgroups of a launch, about
-constexpr int kCscBinMaxGridY = 65535;
+using dev::kCscSegmentEntries;
+using dev::kCscThreads;
+constexpr int kCscWaves = kCscThreads / kWave;
 constexpr int kCscBinMaxWindowGroups = 32768;
 
 // one column of a window
@@ -83,24 +77,18 @@ struct CscBinArgs {
   const CscZeroFeat* zfeats;
 };
 
-__global__ __launch_bounds__(kCscBinThreads) void k_csc_bin_column_order(CscBinArgs c) {
+__global__ __launch_bounds__(kCscThreads) void k_csc_bin_column_order(CscBinArgs c) {
   for (int it = blockIdx.y; it < c.num_items; it += gridDim.y) {
     const CscBinItem I = c.items[it];
-    bool descends = false;
-    for (int64_t i = I.begin + blockIdx.x * static_cast<int64_t>(kCscBinThreads) + threadIdx.x; i + 1 < I.end;
-         i += gridDim.x * static_cast<int64_t>(kCscBinThreads)) {
-      descends |= c.indices[i] >= c.indices[i + 1];
-    }
-    // (the flag starts as all ones; whoever finds a pair out of order clears it)
-    if (descends) atomicAnd(&c.ascending[it], 0u);
+    dev::ClearUnlessAscending(c.indices, I.begin, I.end, &c.ascending[it]);
   }
 }
 
 template <typename T>
-__global__ __launch_bounds__(kCscBinThreads) void k_csc_to_group_bins(CscBinArgs c) {
+__global__ __launch_bounds__(kCscThreads) void k_csc_to_group_bins(CscBinArgs c) {
   const int lane = threadIdx.x & (kWave - 1);
-  const int64_t wave = blockIdx.x * static_cast<int64_t>(kCscBinWaves) + (threadIdx.x >> 6);
-  const int64_t stride = gridDim.x * static_cast<int64_t>(kCscBinWaves) * kCscBinSegmentEntries;
+  const int64_t wave = blockIdx.x * static_cast<int64_t>(kCscWaves) + (threadIdx.x >> 6);
+  const int64_t num_waves = gridDim.x * static_cast<int64_t>(kCscWaves);
   const T* data = static_cast<const T*>(c.data);
   for (int it = blockIdx.y; it < c.num_items; it += gridDim.y) {
     const CscBinItem I = c.items[it];
@@ -108,47 +96,18 @@ __global__ __launch_bounds__(kCscBinThreads) void k_csc_to_group_bins(CscBinArgs
     const CsrBinGroup G = c.groups[F.group];
     uint32_t* named = I.pz_slot >= 0 ? c.named + I.pz_slot * c.named_words : nullptr;
     int group;
-    if (c.ascending[it] != 0u) {
-      for (int64_t b = I.begin + wave * kCscBinSegmentEntries; b < I.end; b += stride) {
-        const int64_t end = b + kCscBinSegmentEntries < I.end ? b + kCscBinSegmentEntries : I.end;
-        for (int64_t i = b + lane; i < end; i += kWave) {
-          const int64_t r = dev::CscBinEntryRow(c.indices[i], c.num_row);
-          if (r < 0) continue;
+    int64_t r = -1;
+    uint32_t cell = 0u;
+    dev::WalkColumn(
+        c.indices, I.begin, I.end, c.ascending[it] != 0u, wave, num_waves, lane,
+        [](int64_t, int64_t) { return false; },  // (all rows of the matrix: no segment is skipped)
+        [&](int64_t i, int32_t index) {
+          r = dev::CscBinEntryRow(index, c.num_row);
+          if (r < 0) return false;
           if (named != nullptr) atomicOr(&named[r >> 5], 1u << (r & 31));
-          uint32_t cell;
-          if (dev::CsrFeatWrite(c.t, F, static_cast<double>(data[i]), &group, &cell)) StoreCell(c.scratch, G, r, cell);
-        }
-      }
-      continue;
-    }
-    if (wave != 0) continue;  // (the whole wave)
-    for (int64_t b = I.begin; b < I.end; b += kWave) {
-      const int64_t i = b + lane;
-      int32_t index = 0;
-      int64_t r = -1;
-      uint32_t cell = 0u;
-      bool kept = false;
-      if (i < I.end) {
-        index = c.indices[i];
-        r = dev::CscBinEntryRow(index, c.num_row);
-        if (r >= 0) {
-          if (named != nullptr) atomicOr(&named[r >> 5], 1u << (r & 31));
-          kept = dev::CsrFeatWrite(c.t, F, static_cast<double>(data[i]), &group, &cell);
-        }
-      }
-      // of the batch's lanes writing one row only the highest (the last stored entry) stores
-      bool write = kept;
-      unsigned long long pending = __ballot(kept);
-      while (pending != 0ull) {
-        const int32_t lead = dev::ReadLane(index, __ffsll(pending) - 1);
-        const unsigned long long same = __ballot(kept && index == lead);
-        if (kept && index == lead && (same >> lane) > 1ull) write = false;
-        pending &= ~same;
-      }
-      if (write) StoreCell(c.scratch, G, r, cell);
-      // (this batch's stores are done before the next batch's are issued)
-      if (b + kWave < I.end) __threadfence_block();
-    }
+          return dev::CsrFeatWrite(c.t, F, static_cast<double>(data[i]), &group, &cell);
+        },
+        [&](int64_t) { StoreCell(c.scratch, G, r, cell); });
   }
 }
 
@@ -266,16 +225,16 @@ class CscWindow {
       c.num_items = static_cast<int32_t>(items.size());
       long long longest = 0;
       for (long long l : launch_longest) longest = std::max(longest, l);
-      hipLaunchKernelGGL(k_csc_bin_column_order, Grid(c.num_items, longest, kCscBinThreads), dim3(kCscBinThreads), 0, 0, c);
+      hipLaunchKernelGGL(k_csc_bin_column_order, dev::CscGrid(c.num_items, longest, kCscThreads), dim3(kCscThreads), 0, 0, c);
       const CscBinItem* d_items = c.items;
       uint32_t* d_ascending = c.ascending;
       for (size_t m = 0; m + 1 < launch_start.size(); ++m) {
         c.items = d_items + launch_start[m];
         c.ascending = d_ascending + launch_start[m];
         c.num_items = static_cast<int32_t>(launch_start[m + 1] - launch_start[m]);
-        const dim3 grid = Grid(c.num_items, launch_longest[m], static_cast<int64_t>(kCscBinWaves) * kCscBinSegmentEntries);
-        if (is_f64) hipLaunchKernelGGL((k_csc_to_group_bins<double>), grid, dim3(kCscBinThreads), 0, 0, c);
-        else hipLaunchKernelGGL((k_csc_to_group_bins<float>), grid, dim3(kCscBinThreads), 0, 0, c);
+        const dim3 grid = dev::CscGrid(c.num_items, launch_longest[m], static_cast<int64_t>(kCscWaves) * kCscSegmentEntries);
+        if (is_f64) hipLaunchKernelGGL((k_csc_to_group_bins<double>), grid, dim3(kCscThreads), 0, 0, c);
+        else hipLaunchKernelGGL((k_csc_to_group_bins<float>), grid, dim3(kCscThreads), 0, 0, c);
       }
       GROUPBINCHECK(hipGetLastError());
     }
@@ -297,13 +256,6 @@ class CscWindow {
   }
 
  private:
-  static dim3 Grid(int num_items, long long longest, int64_t entries_per_block) {
-    const int64_t blocks = (longest + entries_per_block - 1) / entries_per_block;
-    const int64_t cap = std::max<int64_t>(1, kCscBinGridBlocks / num_items);
-    return dim3(static_cast<unsigned>(std::max<int64_t>(1, std::min(blocks, cap))),
-                static_cast<unsigned>(std::min(num_items, kCscBinMaxGridY)));
-  }
-
   const HostTables& h_;
   const std::vector<std::vector<std::pair<int, int32_t>>>& members_;
   DeviceScope* sc_;
@@ -318,14 +270,13 @@ void CheckCscTypes(int col_ptr_type, int data_type) {
 }
 
 // every column's clamped entry range (csc_slots.h CscColumnRange)
-void ColumnRanges(const void* col_ptr, bool ptr_64, int64_t ncol, int64_t nelem, std::vector<long long>* begin,
+void ColumnRanges(SparsePtr col_ptr, int64_t ncol, int64_t nelem, std::vector<long long>* begin,
                   std::vector<long long>* end) {
   begin->assign(static_cast<size_t>(ncol), 0);
   end->assign(static_cast<size_t>(ncol), 0);
   for (int64_t col = 0; col < ncol; ++col) {
     int64_t s, e;
-    if (ptr_64) dev::CscColumnRange(static_cast<const int64_t*>(col_ptr), static_cast<int>(col), nelem, &s, &e);
-    else dev::CscColumnRange(static_cast<const int32_t*>(col_ptr), static_cast<int>(col), nelem, &s, &e);
+    dev::CscColumnRange(col_ptr, static_cast<int>(col), nelem, &s, &e);
     (*begin)[col] = s;
     (*end)[col] = e;
   }
@@ -341,25 +292,17 @@ void DeviceBinCscStats(int64_t* csc_calls, int64_t* column_samples) {
 }
 
 void CscBinLaunchInfo(int64_t* out) {
-  out[0] = kCscBinSegmentEntries;
+  out[0] = kCscSegmentEntries;
   out[1] = kMaxPushZeroFeatures;
   out[2] = kTileRows;
-  out[3] = kCscBinThreads;
+  out[3] = kCscThreads;
   out[4] = kWave;
 }
 
 bool CscPointerValid(const void* col_ptr, int col_ptr_type, int64_t ncol_ptr, int64_t nelem) {
   if (col_ptr == nullptr || ncol_ptr < 1 || nelem < 0) return false;
   if (col_ptr_type != C_API_DTYPE_INT32 && col_ptr_type != C_API_DTYPE_INT64) return false;
-  auto ptr_at = [=](int64_t i) -> int64_t {
-    return col_ptr_type == C_API_DTYPE_INT64 ? static_cast<const int64_t*>(col_ptr)[i]
-                                             : static_cast<const int32_t*>(col_ptr)[i];
-  };
-  if (ptr_at(0) < 0 || ptr_at(ncol_ptr - 1) > nelem) return false;
-  for (int64_t c = 0; c + 1 < ncol_ptr; ++c) {
-    if (ptr_at(c + 1) < ptr_at(c)) return false;
-  }
-  return true;
+  return PointerValid(SparsePtr{col_ptr, col_ptr_type == C_API_DTYPE_INT64}, ncol_ptr - 1, nelem);
 }
 
 void EvalCscGroupBins(const Dataset& ds, const void* col_ptr, int col_ptr_type, const int32_t* indices,
@@ -371,17 +314,10 @@ void EvalCscGroupBins(const Dataset& ds, const void* col_ptr, int col_ptr_type, 
   const CsrBinTables t = h.View();
   const int ng = ds.num_groups();
   std::vector<int32_t> part(static_cast<size_t>(num_row) * std::max(1, t.num_groups));
-  auto run = [&](auto* ptr, auto* val) {
-    dev::EvalCscToGroupBins(ptr, ncol_ptr - 1, indices, val, nelem, num_row, t, part.data());
-  };
-  const bool f64 = data_type == C_API_DTYPE_FLOAT64;
-  if (col_ptr_type == C_API_DTYPE_INT64) {
-    if (f64) run(static_cast<const int64_t*>(col_ptr), static_cast<const double*>(data));
-    else run(static_cast<const int64_t*>(col_ptr), static_cast<const float*>(data));
-  } else {
-    if (f64) run(static_cast<const int32_t*>(col_ptr), static_cast<const double*>(data));
-    else run(static_cast<const int32_t*>(col_ptr), static_cast<const float*>(data));
-  }
+  DispatchSparse(col_ptr_type == C_API_DTYPE_INT64, data_type == C_API_DTYPE_FLOAT64, col_ptr, data,
+                 [&](auto* ptr, auto* val) {
+                   dev::EvalCscToGroupBins(ptr, ncol_ptr - 1, indices, val, nelem, num_row, t, part.data());
+                 });
   for (int64_t r = 0; r < num_row; ++r) {
     for (int g = 0; g < ng; ++g) bins[r * ng + g] = h.col_of[g] < 0 ? -1 : part[r * t.num_groups + h.col_of[g]];
   }
@@ -402,7 +338,7 @@ void CscGroupBinsOnDevice(const Dataset& ds, const void* d_col_ptr, int col_ptr_
   std::vector<char> col_ptr(static_cast<size_t>(ncol_ptr) * (ptr_64 ? sizeof(int64_t) : sizeof(int32_t)));
   GROUPBINCHECK(hipMemcpy(col_ptr.data(), d_col_ptr, col_ptr.size(), hipMemcpyDeviceToHost));
   std::vector<long long> begin, end;
-  ColumnRanges(col_ptr.data(), ptr_64, ncol_ptr - 1, nelem, &begin, &end);
+  ColumnRanges(SparsePtr{col_ptr.data(), ptr_64}, ncol_ptr - 1, nelem, &begin, &end);
   DeviceScope sc;
   std::vector<CsrBinGroup> groups;
   const int64_t bytes = PlaceColumns(ds, h, num_row, &groups);
@@ -439,7 +375,7 @@ std::vector<char> DeviceBinCscMatrix(Dataset* ds, const void* col_ptr, int col_p
   const size_t esz = is_f64 ? sizeof(double) : sizeof(float);
   const int64_t ncol = ncol_ptr - 1;
   std::vector<long long> begin, end;  // in the caller's arrays
-  ColumnRanges(col_ptr, ptr_64, ncol, nelem, &begin, &end);
+  ColumnRanges(SparsePtr{col_ptr, ptr_64}, ncol, nelem, &begin, &end);
   const auto members = GroupMembers(h, ncol);
   DeviceScope sc;
   CscWindow window(h, members, &sc);
@@ -490,8 +426,9 @@ std::vector<char> DeviceBinCscMatrix(Dataset* ds, const void* col_ptr, int col_p
   StoredCellLists lists(&sc, cap_sparse, num_row);
   std::vector<CsrBinGroup> groups;
   std::vector<long long> d_begin(static_cast<size_t>(ncol), 0), d_end(static_cast<size_t>(ncol), 0);
-  std::vector<int> cols;
-  std::vector<int32_t> sparse_groups;
+  std::vector<int32_t> cols, sparse_groups;
+  std::vector<ColumnRun> runs;
+  std::vector<int64_t> placed;
   std::vector<uint8_t> staged;
   for (size_t w = 0; w + 1 < win.size(); ++w) {
     const size_t k0 = win[w], k1 = win[w + 1];
@@ -503,25 +440,17 @@ std::vector<char> DeviceBinCscMatrix(Dataset* ds, const void* col_ptr, int col_p
       if (ds->group(h.gid[k]).sparse) sparse_groups.push_back(static_cast<int32_t>(k));
     }
     std::sort(cols.begin(), cols.end());
-    long long at = 0;
-    for (size_t j = 0; j < cols.size();) {
-      const long long src = begin[cols[j]];
-      long long stop = end[cols[j]];
-      size_t j1 = j + 1;
-      while (j1 < cols.size() && begin[cols[j1]] == stop) stop = end[cols[j1++]];
-      for (size_t q = j; q < j1; ++q) {
-        d_begin[cols[q]] = at + (begin[cols[q]] - src);
-        d_end[cols[q]] = at + (end[cols[q]] - src);
-      }
-      if (stop > src) {
-        GROUPBINCHECK(hipMemcpy(d_indices + at, indices + src, sizeof(int32_t) * static_cast<size_t>(stop - src),
-                                hipMemcpyHostToDevice));
-        GROUPBINCHECK(hipMemcpy(d_data + esz * static_cast<size_t>(at),
-                                static_cast<const char*>(data) + esz * static_cast<size_t>(src),
-                                esz * static_cast<size_t>(stop - src), hipMemcpyHostToDevice));
-      }
-      at += stop - src;
-      j = j1;
+    PackColumnRuns(cols, SparsePtr{col_ptr, ptr_64}, ncol, &runs, &placed);
+    for (size_t j = 0; j < cols.size(); ++j) {
+      d_begin[cols[j]] = placed[j];
+      d_end[cols[j]] = placed[j + 1];
+    }
+    for (const ColumnRun& r : runs) {
+      GROUPBINCHECK(hipMemcpy(d_indices + r.dst, indices + r.src, sizeof(int32_t) * static_cast<size_t>(r.len),
+                              hipMemcpyHostToDevice));
+      GROUPBINCHECK(hipMemcpy(d_data + esz * static_cast<size_t>(r.dst),
+                              static_cast<const char*>(data) + esz * static_cast<size_t>(r.src),
+                              esz * static_cast<size_t>(r.len), hipMemcpyHostToDevice));
     }
     const int64_t scratch_bytes = PlaceColumns(*ds, h, num_row, &groups, k0, k1);
     GROUPBINCHECK(hipMemsetAsync(c.scratch, 0, static_cast<size_t>(std::max<int64_t>(1, scratch_bytes)), 0));

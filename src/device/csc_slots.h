@@ -12,29 +12,21 @@
 #include <algorithm>
 #include <cstdint>
 
-// (as in forest_decision.h; this header needs nothing else of the device's, so that a plain C++
-// program can include it: tests/native/csc_slots_driver.cpp)
-#if defined(__HIPCC__)
-#define LGBM_AMD_HD __host__ __device__ __forceinline__
-#else
-#define LGBM_AMD_HD inline
-#endif
+// (a plain C++ program can include this header: tests/native/csc_slots_driver.cpp)
+#include "stored_order.h"
 
 namespace lgbm_amd {
 namespace dev {
 
 // the entries [*s, *e) of column `col` of the pointer (col < 0: the slot's feature is no column
 // of the matrix, which has no entries), kept inside num_entries whatever col_ptr holds
-template <typename P>
-LGBM_AMD_HD void CscColumnRange(const P* col_ptr, int col, int64_t num_entries, int64_t* s, int64_t* e) {
+template <typename Ptr>
+LGBM_AMD_HD void CscColumnRange(Ptr col_ptr, int col, int64_t num_entries, int64_t* s, int64_t* e) {
   if (col < 0) {
     *s = *e = 0;
     return;
   }
-  const int64_t a = static_cast<int64_t>(col_ptr[col]);
-  const int64_t b = static_cast<int64_t>(col_ptr[col + 1]);
-  *s = a < 0 ? 0 : (a > num_entries ? num_entries : a);
-  *e = b < *s ? *s : (b > num_entries ? num_entries : b);
+  ClampedRange(col_ptr, col, 0, num_entries, s, e);
 }
 
 // the row of a stored entry inside the chunk of rows [row0, row0 + rows), or -1: another chunk's

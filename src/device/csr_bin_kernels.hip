@@ -6,13 +6,12 @@
 //                        bin by binary search over the upper bounds in global memory (they do
 //                        not fit LDS for wide inputs), the group cell.  The rows of a chunk go
 //                        into a zero-filled scratch of one column per group ([group][row], the
-//                        group's bin_bytes per cell).  Of a batch's lanes writing one group only
-//                        the highest stores (ballots), and between batches the wave waits for
-//                        its stores (a workgroup fence), so the last stored write wins on every
-//                        run, as in k_csr_to_slots.  The features whose zeros are pushed
-//                        (default bin != most frequent bin) are flagged in a per-wave LDS bitset
-//                        by the entries that name them; after the entries the unflagged ones
-//                        write the bin of 0.0, 64 per batch by the same store rule.
+//                        group's bin_bytes per cell).  The last stored write to a cell wins on
+//                        every run: src/device/stored_order.h, LastOfKey on the group and
+//                        BatchFence.  The features whose zeros are pushed (default bin != most
+//                        frequent bin) are flagged in a per-wave LDS bitset by the entries that
+//                        name them; after the entries the unflagged ones write the bin of 0.0,
+//                        64 per batch by the same store rule.
 // The compaction of sparse groups (k_count_stored / k_scan_counts / k_write_stored), the dense
 // groups' column copy-back and the host tables are shared with the CSC path:
 // src/device/group_bin_scratch.h.  Rows stream through in chunks whose entries and scratch each
@@ -31,6 +30,7 @@
 #include "lgbm_amd/dataset.h"
 #include "lgbm_amd/device_binning.h"
 #include "lgbm_amd/log.h"
+#include "lgbm_amd/sparse_ptr.h"
 #include "lgbm_amd/tuning.h"
 
 namespace lgbm_amd {
@@ -54,18 +54,9 @@ struct CsrBinArgs {
   uint8_t* scratch;
 };
 
-// one batch of a wave's writes to the cells of `row` (group < 0: the lane writes nothing): of the
-// lanes on one group only the highest, the last in stored order, stores
+// one batch of a wave's writes to the cells of `row` (group < 0: the lane writes nothing)
 __device__ __forceinline__ void StoreBatch(const CsrBinArgs& c, int64_t row, int lane, int group, uint32_t cell) {
-  bool write = group >= 0;
-  unsigned long long pending = __ballot(group >= 0);
-  while (pending != 0ull) {
-    const int lead = dev::ReadLane(group, __ffsll(pending) - 1);
-    const unsigned long long same = __ballot(group == lead);
-    if (group == lead && (same >> lane) > 1ull) write = false;
-    pending &= ~same;
-  }
-  if (write) StoreCell(c.scratch, c.groups[group], row, cell);
+  if (dev::LastOfKey(lane, group)) StoreCell(c.scratch, c.groups[group], row, cell);
 }
 
 template <typename T, typename P>
@@ -81,7 +72,7 @@ __global__ __launch_bounds__(kCsrBinThreads) void k_csr_to_group_bins(CsrBinArgs
     __threadfence_block();  // (the wave's LDS writes are done before its flags are set)
   }
   int64_t s, e;
-  dev::CsrBinRowRange(static_cast<const P*>(c.indptr), c.entry_base, c.num_entries, row, &s, &e);
+  dev::ClampedRange(static_cast<const P*>(c.indptr), row, c.entry_base, c.num_entries, &s, &e);
   const T* data = static_cast<const T*>(c.data);
   for (int64_t b = s; b < e; b += kWave) {
     const int64_t i = b + lane;
@@ -96,8 +87,8 @@ __global__ __launch_bounds__(kCsrBinThreads) void k_csr_to_group_bins(CsrBinArgs
       }
     }
     StoreBatch(c, row, lane, group, cell);
-    // (this batch's stores and flags are done before the next batch, or the zeros, are issued)
-    if (b + kWave < e || npz > 0) __threadfence_block();
+    // (before the next batch stores -- and before the zeros read this batch's flags)
+    if (b + kWave < e || npz > 0) dev::BatchFence();
   }
   for (int k0 = 0; k0 < npz; k0 += kWave) {
     const int k = k0 + lane;
@@ -108,7 +99,7 @@ __global__ __launch_bounds__(kCsrBinThreads) void k_csr_to_group_bins(CsrBinArgs
       if (!dev::CsrFeatWrite(c.t, F, 0.0, &group, &cell)) group = -1;
     }
     StoreBatch(c, row, lane, group, cell);
-    if (k0 + kWave < npz) __threadfence_block();
+    if (k0 + kWave < npz) dev::BatchFence();
   }
 }
 
@@ -117,13 +108,10 @@ __global__ __launch_bounds__(kCsrBinThreads) void k_csr_to_group_bins(CsrBinArgs
 void LaunchCsrToGroupBins(const CsrBinArgs& c, bool is_f64, bool indptr_64) {
   const dim3 grid(static_cast<unsigned>((c.num_rows + kCsrBinRowsPerBlock - 1) / kCsrBinRowsPerBlock));
   const dim3 block(kCsrBinThreads);
-  if (is_f64) {
-    if (indptr_64) hipLaunchKernelGGL((k_csr_to_group_bins<double, int64_t>), grid, block, 0, 0, c);
-    else hipLaunchKernelGGL((k_csr_to_group_bins<double, int32_t>), grid, block, 0, 0, c);
-  } else {
-    if (indptr_64) hipLaunchKernelGGL((k_csr_to_group_bins<float, int64_t>), grid, block, 0, 0, c);
-    else hipLaunchKernelGGL((k_csr_to_group_bins<float, int32_t>), grid, block, 0, 0, c);
-  }
+  DispatchSparse(indptr_64, is_f64, c.indptr, c.data, [&](auto* ptr, auto* val) {
+    hipLaunchKernelGGL((k_csr_to_group_bins<std::decay_t<decltype(*val)>, std::decay_t<decltype(*ptr)>>), grid, block, 0,
+                       0, c);
+  });
   CSRBINCHECK(hipGetLastError());
 }
 
@@ -146,15 +134,10 @@ void EvalCsrGroupBins(const Dataset& ds, const void* indptr, int indptr_type, co
   std::vector<int32_t> part(static_cast<size_t>(kRows) * std::max(1, t.num_groups));
   for (int64_t r0 = 0; r0 < nrow; r0 += kRows) {
     const int64_t rows = std::min(kRows, nrow - r0);
-    auto run = [&](auto* ptr, auto* val) { dev::EvalCsrToGroupBins(ptr + r0, 0, indices, val, rows, nelem, t, part.data()); };
-    const bool f64 = data_type == C_API_DTYPE_FLOAT64;
-    if (indptr_type == C_API_DTYPE_INT64) {
-      if (f64) run(static_cast<const int64_t*>(indptr), static_cast<const double*>(data));
-      else run(static_cast<const int64_t*>(indptr), static_cast<const float*>(data));
-    } else {
-      if (f64) run(static_cast<const int32_t*>(indptr), static_cast<const double*>(data));
-      else run(static_cast<const int32_t*>(indptr), static_cast<const float*>(data));
-    }
+    DispatchSparse(indptr_type == C_API_DTYPE_INT64, data_type == C_API_DTYPE_FLOAT64, indptr, data,
+                   [&](auto* ptr, auto* val) {
+                     dev::EvalCsrToGroupBins(ptr + r0, 0, indices, val, rows, nelem, t, part.data());
+                   });
     for (int64_t r = 0; r < rows; ++r) {
       for (int g = 0; g < ng; ++g) {
         bins[(r0 + r) * ng + g] = h.col_of[g] < 0 ? -1 : part[r * t.num_groups + h.col_of[g]];
@@ -204,14 +187,8 @@ std::vector<char> DeviceBinCsrMatrix(Dataset* ds, const void* indptr, int indptr
   const int device = BinningDevice(cfg);
   if (device < 0 || nrow <= 0 || nelem < 0) return done;
   const bool indptr_64 = indptr_type == C_API_DTYPE_INT64, is_f64 = data_type == C_API_DTYPE_FLOAT64;
-  auto ptr_at = [=](int64_t i) -> int64_t {
-    return indptr_64 ? static_cast<const int64_t*>(indptr)[i] : static_cast<const int32_t*>(indptr)[i];
-  };
-  // indptr before any upload: inside [0, nelem] and non-decreasing, or the host takes the matrix
-  if (ptr_at(0) < 0 || ptr_at(nrow) > nelem) return done;
-  for (int64_t r = 0; r < nrow; ++r) {
-    if (ptr_at(r + 1) < ptr_at(r)) return done;
-  }
+  const SparsePtr ptr{indptr, indptr_64};
+  if (!PointerValid(ptr, nrow, nelem)) return done;  // (before any upload: the host takes the matrix)
   const HostTables h(*ds);
   if (h.gid.empty() || static_cast<int>(h.push_zero.size()) > kMaxPushZeroFeatures) return done;
   std::vector<int32_t> sparse_groups;  // eligible groups stored sparse
@@ -235,17 +212,17 @@ std::vector<char> DeviceBinCsrMatrix(Dataset* ds, const void* indptr, int indptr
   while (chunk_start.back() < nrow) {
     const int64_t r0 = chunk_start.back();
     int64_t r1 = std::min(nrow, r0 + max_rows);
-    if (ptr_at(r1) - ptr_at(r0) > max_entries) {  // the last row that keeps the entries under the cap
-      int64_t lo = r0 + 1, hi = r1;               // (at least one row)
+    if (ptr[r1] - ptr[r0] > max_entries) {  // the last row that keeps the entries under the cap
+      int64_t lo = r0 + 1, hi = r1;         // (at least one row)
       while (lo < hi) {
         const int64_t mid = (lo + hi + 1) / 2;
-        if (ptr_at(mid) - ptr_at(r0) <= max_entries) lo = mid;
+        if (ptr[mid] - ptr[r0] <= max_entries) lo = mid;
         else hi = mid - 1;
       }
       r1 = lo;
     }
     cap_rows = std::max(cap_rows, r1 - r0);
-    cap_entries = std::max(cap_entries, ptr_at(r1) - ptr_at(r0));
+    cap_entries = std::max(cap_entries, ptr[r1] - ptr[r0]);
     chunk_start.push_back(r1);
   }
   DeviceScope sc;
@@ -265,7 +242,7 @@ std::vector<char> DeviceBinCsrMatrix(Dataset* ds, const void* indptr, int indptr
   StoredCellLists lists(&sc, nsg, cap_rows);
   for (size_t ch = 0; ch + 1 < chunk_start.size(); ++ch) {
     const int64_t r0 = chunk_start[ch], rows = chunk_start[ch + 1] - r0;
-    const int64_t e0 = ptr_at(r0), entries = ptr_at(r0 + rows) - e0;
+    const int64_t e0 = ptr[r0], entries = ptr[r0 + rows] - e0;
     CSRBINCHECK(hipMemcpy(d_indptr, static_cast<const char*>(indptr) + psz * static_cast<size_t>(r0),
                           psz * static_cast<size_t>(rows + 1), hipMemcpyHostToDevice));
     if (entries > 0) {

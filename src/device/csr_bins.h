@@ -4,8 +4,10 @@
 // to the groups whose members are all numerical (a categorical member keeps its group on the
 // host):
 //   - every group bin of the row starts at 0;
-//   - the stored entries are taken in stored order; one whose column is negative, is not below
-//     num_total_features or maps to no feature of those groups is dropped;
+//   - the stored entries (those between the row's pointers, relative to the chunk's first entry
+//     and clamped to its num_entries: stored_order.h ClampedRange) are taken in stored order; one
+//     whose column is negative, is not below num_total_features or maps to no feature of those
+//     groups is dropped;
 //   - the value as double goes through ValueToBinNumerical (BinMapper::ValueToBin: NaN to the NaN
 //     bin or to 0.0, the binary search over the upper bounds);
 //   - a bin equal to the feature's most frequent bin writes nothing (an earlier write to the cell,
@@ -21,27 +23,11 @@
 #include <cstdint>
 #include <vector>
 
-// (as in forest_decision.h; this header needs nothing else of the device's, so that a plain C++
-// program can include it: tests/native/csr_bins_driver.cpp)
-#if defined(__HIPCC__)
-#define LGBM_AMD_HD __host__ __device__ __forceinline__
-#else
-#define LGBM_AMD_HD inline
-#endif
+// (a plain C++ program can include this header: tests/native/csr_bins_driver.cpp)
+#include "stored_order.h"
 
 namespace lgbm_amd {
 namespace dev {
-
-// a row's entries [*s, *e) relative to the chunk's first entry, kept inside the chunk's
-// num_entries whatever indptr holds (csr_slots.h CsrRowRange)
-template <typename P>
-LGBM_AMD_HD void CsrBinRowRange(const P* indptr, int64_t entry_base, int64_t num_entries, int64_t row, int64_t* s,
-                                int64_t* e) {
-  const int64_t a = static_cast<int64_t>(indptr[row]) - entry_base;
-  const int64_t b = static_cast<int64_t>(indptr[row + 1]) - entry_base;
-  *s = a < 0 ? 0 : (a > num_entries ? num_entries : a);
-  *e = b < *s ? *s : (b > num_entries ? num_entries : b);
-}
 
 // a numerical feature of a device-eligible group
 struct CsrBinFeat {
@@ -109,7 +95,7 @@ void EvalCsrToGroupBins(const P* indptr, int64_t entry_base, const int32_t* indi
     int32_t* o = out + r * t.num_groups;
     std::fill(named.begin(), named.end(), 0);
     int64_t s, e;
-    CsrBinRowRange(indptr, entry_base, num_entries, r, &s, &e);
+    ClampedRange(indptr, r, entry_base, num_entries, &s, &e);
     int group;
     uint32_t cell;
     for (int64_t i = s; i < e; ++i) {

@@ -8,13 +8,12 @@
 //
 // One wave per row reads 64 consecutive entries at a time (coalesced; half the time of one
 // thread per row at 40 entries per row).  Of a row's entries on one column the last stored one
-// wins (the host predictor's Predictor::Fill), on every run: within a batch of 64 the lanes
-// holding one slot are found with ballots and only the highest of them stores; between batches
-// the wave waits until its stores have been acknowledged (a workgroup fence: s_waitcnt vmcnt(0),
-// which counts every lane's stores), so a later batch's store to a cell reaches memory after an
-// earlier batch's.  (profiles/r08_device_sparse_predict.md has the layouts and mappings measured.)
+// wins (the host predictor's Predictor::Fill), on every run: src/device/stored_order.h, LastOfKey
+// on the slot and BatchFence.  (profiles/r08_device_sparse_predict.md has the layouts and
+// mappings measured.)
 #include "csr_slots.h"
 #include "device_common.h"
+#include "lgbm_amd/sparse_ptr.h"
 
 namespace lgbm_amd {
 namespace dev {
@@ -30,7 +29,7 @@ __global__ __launch_bounds__(kCsrThreads) void k_csr_to_slots(CsrSlotsArgs c) {
   const int64_t row = blockIdx.x * static_cast<int64_t>(kCsrRowsPerBlock) + (threadIdx.x >> 6);
   if (row >= c.num_rows) return;  // (the whole wave)
   int64_t s, e;
-  CsrRowRange(static_cast<const P*>(c.indptr), c.entry_base, c.num_entries, row, &s, &e);
+  ClampedRange(static_cast<const P*>(c.indptr), row, c.entry_base, c.num_entries, &s, &e);
   const T* data = static_cast<const T*>(c.data);
   T* out = static_cast<T*>(c.out);
   for (int64_t b = s; b < e; b += kWave) {
@@ -41,18 +40,8 @@ __global__ __launch_bounds__(kCsrThreads) void k_csr_to_slots(CsrSlotsArgs c) {
       slot = CsrEntrySlot(c.slot_of, c.num_features, c.indices[i]);
       v = data[i];
     }
-    // of the batch's lanes on one slot only the highest (the last stored entry) writes
-    bool write = slot >= 0;
-    unsigned long long pending = __ballot(slot >= 0);
-    while (pending != 0ull) {
-      const int lead_slot = ReadLane(slot, __ffsll(pending) - 1);
-      const unsigned long long same = __ballot(slot == lead_slot);
-      if (slot == lead_slot && (same >> lane) > 1ull) write = false;
-      pending &= ~same;
-    }
-    if (write) out[static_cast<int64_t>(slot) * c.num_rows + row] = v;
-    // (this batch's stores are done before the next batch's are issued)
-    if (b + kWave < e) __threadfence_block();
+    if (LastOfKey(lane, slot)) out[static_cast<int64_t>(slot) * c.num_rows + row] = v;
+    if (b + kWave < e) BatchFence();
   }
 }
 
@@ -69,13 +58,9 @@ void CsrToSlots(const CsrSlotsArgs& c, hipStream_t s) {
   const size_t bytes = static_cast<size_t>(c.num_rows) * c.num_slots * (c.is_double ? 8 : 4);
   (void)hipMemsetAsync(c.out, 0, bytes, s);
   if (c.num_entries <= 0) return;
-  if (c.is_double) {
-    if (c.indptr_is_64) Launch<double, int64_t>(c, s);
-    else Launch<double, int32_t>(c, s);
-  } else {
-    if (c.indptr_is_64) Launch<float, int64_t>(c, s);
-    else Launch<float, int32_t>(c, s);
-  }
+  DispatchSparse(c.indptr_is_64 != 0, c.is_double != 0, c.indptr, c.data, [&](auto* ptr, auto* val) {
+    Launch<std::decay_t<decltype(*val)>, std::decay_t<decltype(*ptr)>>(c, s);
+  });
 }
 
 }  // namespace dev

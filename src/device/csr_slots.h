@@ -11,7 +11,7 @@
 #include <algorithm>
 #include <cstdint>
 
-#include "forest_decision.h"
+#include "stored_order.h"
 
 namespace lgbm_amd {
 namespace dev {
@@ -22,26 +22,16 @@ LGBM_AMD_HD int CsrEntrySlot(const int32_t* slot_of, int num_features, int col) 
   return col >= 0 && col < num_features ? slot_of[col] : -1;
 }
 
-// a row's entries [*s, *e) relative to the chunk's first entry, kept inside the chunk's
-// num_entries whatever indptr holds
-template <typename P>
-LGBM_AMD_HD void CsrRowRange(const P* indptr, int64_t entry_base, int64_t num_entries, int64_t row, int64_t* s,
-                             int64_t* e) {
-  const int64_t a = static_cast<int64_t>(indptr[row]) - entry_base;
-  const int64_t b = static_cast<int64_t>(indptr[row + 1]) - entry_base;
-  *s = a < 0 ? 0 : (a > num_entries ? num_entries : a);
-  *e = b < *s ? *s : (b > num_entries ? num_entries : b);
-}
-
 // the kernel's result on the host, row-major (the kernel's matrix is column-major): `out`
-// ([rows][num_slots]) zero-filled, then every stored entry with a slot written in stored order
+// ([rows][num_slots]) zero-filled, then every stored entry with a slot written in stored order; a
+// row's entries are relative to the chunk's first entry and clamped to its num_entries
 template <typename T, typename P>
 void EvalCsrToSlots(const P* indptr, int64_t entry_base, const int32_t* indices, const T* data, int64_t rows,
                     int64_t num_entries, const int32_t* slot_of, int num_features, int num_slots, T* out) {
   std::fill(out, out + rows * num_slots, T(0));
   for (int64_t r = 0; r < rows; ++r) {
     int64_t s, e;
-    CsrRowRange(indptr, entry_base, num_entries, r, &s, &e);
+    ClampedRange(indptr, r, entry_base, num_entries, &s, &e);
     for (int64_t i = s; i < e; ++i) {
       const int slot = CsrEntrySlot(slot_of, num_features, indices[i]);
       if (slot >= 0) out[r * num_slots + slot] = data[i];

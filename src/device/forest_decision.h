@@ -9,12 +9,7 @@
 #include <cmath>
 
 #include "kernels.h"
-
-#if defined(__HIPCC__)
-#define LGBM_AMD_HD __host__ __device__ __forceinline__
-#else
-#define LGBM_AMD_HD inline
-#endif
+#include "stored_order.h"  // (LGBM_AMD_HD)
 
 namespace lgbm_amd {
 namespace dev {

@@ -642,10 +642,7 @@ void CsrToSlots(const CsrSlotsArgs& c, hipStream_t s);
 // (src/device/csc_slots.h has the rule of an entry; src/device/csc_kernels.hip): a slot's values
 // are the stored entries of one column.  CscColumnOrder writes `ascending` once for arrays that
 // stay on the device; CscToSlots, on the same stream, zero-fills the matrix and scatters a chunk.
-// A column is cut into segments of kCscSegmentEntries stored entries, one wave each; a column
-// whose row indices do not ascend strictly is walked by one wave in stored order
-constexpr int kCscThreads = 256;
-constexpr int kCscSegmentEntries = 512;
+// (src/device/stored_order.h has the walk of a column and its constants)
 struct CscSlotsArgs {
   int32_t col_ptr_is_64{};   // col_ptr: int64 (else int32)
   int32_t is_double{};       // data and out: float64 (else float32)

@@ -2,12 +2,16 @@
 // hand-written hostile matrix of tests/test_csc_slots.py -- cells stored twice and three times,
 // empty columns, a slot without a column, a pointer past the entries, and row indices -1, num_row
 // and 2^31 - 1 -- through EvalCscToSlots for every row window, into a buffer that ends exactly
-// where the matrix ends, so that a write outside it is a heap overflow.
+// where the matrix ends, so that a write outside it is a heap overflow.  Then PackColumnRuns
+// (include/lgbm_amd/sparse_ptr.h), the packing of a set of columns for upload, against a direct
+// computation: adjacent columns, an empty column between two used ones, a gap, used columns past
+// the matrix's width, a single column.
 #include <cmath>
 #include <cstdint>
 #include <cstdio>
 #include <vector>
 
+#include "../../include/lgbm_amd/sparse_ptr.h"
 #include "../../src/device/csc_slots.h"
 
 using lgbm_amd::dev::EvalCscToSlots;
@@ -64,7 +68,55 @@ static void Run(const char* what) {
   EvalCscToSlots(wild.data(), slot_col.data(), indices.data(), data.data(), nelem, 0, num_row, ns, out.data());
 }
 
+// `columns` of the matrix under col_ptr: the runs copy exactly the entries of the columns, in
+// order, to where `placed` says each column lies, and no two runs could have been one
+template <typename P>
+static void Pack(const char* what, const std::vector<P>& col_ptr, const std::vector<int32_t>& columns,
+                 const std::vector<lgbm_amd::ColumnRun>& want_runs) {
+  const int64_t ncol = static_cast<int64_t>(col_ptr.size()) - 1;
+  std::vector<lgbm_amd::ColumnRun> runs;
+  std::vector<int64_t> placed;
+  lgbm_amd::PackColumnRuns(columns, lgbm_amd::SparsePtr{col_ptr.data(), sizeof(P) == 8}, ncol, &runs, &placed);
+  bool ok = placed.size() == columns.size() + 1 && runs.size() == want_runs.size();
+  // the direct computation: entry by entry, column after column
+  std::vector<int64_t> src_of;
+  for (size_t j = 0; ok && j < columns.size(); ++j) {
+    ok = placed[j] == static_cast<int64_t>(src_of.size());
+    if (columns[j] < ncol) {
+      for (int64_t i = col_ptr[columns[j]]; i < col_ptr[columns[j] + 1]; ++i) src_of.push_back(i);
+    }
+    ok = ok && placed[j + 1] == static_cast<int64_t>(src_of.size());
+  }
+  std::vector<int64_t> copied(src_of.size(), -1);
+  for (size_t k = 0; ok && k < runs.size(); ++k) {
+    ok = runs[k].src == want_runs[k].src && runs[k].dst == want_runs[k].dst && runs[k].len == want_runs[k].len &&
+         runs[k].len > 0 && runs[k].dst >= 0 && runs[k].dst + runs[k].len <= static_cast<int64_t>(copied.size());
+    for (int64_t i = 0; ok && i < runs[k].len; ++i) copied[runs[k].dst + i] = runs[k].src + i;
+  }
+  if (!ok || copied != src_of) {
+    std::fprintf(stderr, "pack %s (%zu-byte pointer): wrong runs or places\n", what, sizeof(P));
+    ++failures;
+  }
+}
+
+template <typename P>
+static void PackCases() {
+  // columns 0 .. 6 hold 3, 2, 0, 4, 0, 1, 5 entries
+  const std::vector<P> col_ptr = {0, 3, 5, 5, 9, 9, 10, 15};
+  Pack<P>("adjacent columns merge", col_ptr, {0, 1}, {{0, 0, 5}});
+  Pack<P>("an empty column between two used ones still merges", col_ptr, {1, 3}, {{3, 0, 6}});
+  Pack<P>("an empty used column between two used ones", col_ptr, {1, 2, 3}, {{3, 0, 6}});
+  Pack<P>("a gap gives two runs", col_ptr, {0, 3, 6}, {{0, 0, 3}, {5, 3, 4}, {10, 7, 5}});
+  Pack<P>("used columns past the width", col_ptr, {5, 6, 7, 9}, {{9, 0, 6}});
+  Pack<P>("only columns past the width", col_ptr, {7, 8}, {});
+  Pack<P>("a single column", col_ptr, {3}, {{5, 0, 4}});
+  Pack<P>("a single empty column", col_ptr, {4}, {});
+  Pack<P>("no column", col_ptr, {}, {});
+}
+
 int main() {
+  PackCases<int32_t>();
+  PackCases<int64_t>();
   Run<float, int32_t>("float32 int32");
   Run<float, int64_t>("float32 int64");
   Run<double, int32_t>("float64 int32");

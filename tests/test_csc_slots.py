@@ -164,3 +164,33 @@ def test_single_leaf_model_uses_no_feature():
     m = sp.csc_matrix(c.X[:50])
     used, mat = _slots(c.booster, m.indptr, m.indices, m.data, 50)
     assert used.size == 0 and mat.shape == (50, 0)
+
+
+def test_prediction_and_binning_walk_columns_with_one_set_of_constants():
+    """Both CSC paths walk a column by src/device/stored_order.h: a segment length or a workgroup
+    size of its own on either side would fork the walk again."""
+    from lightgbmv1_amd import ops
+    predict, binning = ops.csc_launch_info(), ops.csc_bin_launch_info()
+    for key in ("segment_entries", "block", "batch"):
+        assert predict[key] == binning[key], key
+
+
+def test_pack_column_runs_native_driver(tmp_path):
+    """PackColumnRuns (include/lgbm_amd/sparse_ptr.h), which both CSC paths upload their columns
+    by, has no entry point of its own: tests/native/csc_slots_driver.cpp checks its runs and every
+    column's place against a direct computation (adjacent columns, an empty column between two
+    used ones, a gap, columns past the matrix's width, a single column).  The plain build of the
+    program; tests/test_csc_slots_sanitized.py has the sanitized one."""
+    import os
+    import shutil
+    import subprocess
+    cxx = shutil.which(os.environ.get("CXX", "g++"))
+    if cxx is None:
+        pytest.skip("no C++ compiler")
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    driver = tmp_path / "csc_slots_driver"
+    build = subprocess.run([cxx, "-std=c++17", "-O1", os.path.join(root, "tests", "native", "csc_slots_driver.cpp"),
+                            "-o", str(driver)], capture_output=True, text=True, timeout=300)
+    assert build.returncode == 0, build.stderr[-4000:]
+    out = subprocess.run([str(driver)], capture_output=True, text=True, timeout=60)
+    assert out.returncode == 0 and "csc slots driver ok" in out.stdout, (out.stdout + out.stderr)[-4000:]
