@@ -231,6 +231,13 @@ LIGHTGBM_C_EXPORT int LGBM_AMD_NetworkFreeThreadHub(void* hub);
 // num_groups + 1 entries); call with null buffers to get num_groups first
 LIGHTGBM_C_EXPORT int LGBM_AMD_DatasetGetGroupBins(DatasetHandle handle, int32_t* bins, int64_t* boundaries,
                                                    int* num_groups);
+// test support (tests/helpers/split_cases.py): what the binning made of every used feature, as a
+// JSON list by inner feature index -- real index, num_bin, missing_type (0 none, 1 zero, 2 NaN),
+// default_bin, most_freq_bin, offset (1: bin 0 is not stored), categorical, group, position in
+// the group and in a leaf's histogram, and the bins' upper bounds or categories.  Read-only, no
+// device needed
+LIGHTGBM_C_EXPORT int LGBM_AMD_DatasetFeatureMeta(DatasetHandle handle, int64_t buffer_len, int64_t* out_len,
+                                                  char* out_str);
 // the state the last device-grown tree left in HBM: a leaf's rows (count first with rows ==
 // null), its raw fixed-point histogram slot (2 * total_bins int64: g, h) and sums
 // (sum_g, sum_h, count); the rows' packed (g, h) and the fixed-point scales

@@ -16,6 +16,7 @@
 #include <memory>
 #include <mutex>
 #include <shared_mutex>
+#include <sstream>
 #include <string>
 #include <unordered_map>
 #include <utility>
@@ -1669,6 +1670,44 @@ int LGBM_AMD_DatasetGetGroupBins(DatasetHandle handle, int32_t* bins, int64_t* b
       for (int g = 0; g < ng; ++g) bins[static_cast<size_t>(r) * ng + g] = static_cast<int32_t>(d->group(g).Get(r));
     }
   }
+  API_END();
+}
+
+int LGBM_AMD_DatasetFeatureMeta(DatasetHandle handle, int64_t buffer_len, int64_t* out_len, char* out_str) {
+  API_BEGIN();
+  const Dataset* d = static_cast<const Dataset*>(handle);
+  std::ostringstream js;
+  js.precision(17);
+  // (JSON has no non-finite numbers: the last upper bound and the NaN bin's are written as the
+  // literals Python's json module reads)
+  auto num = [&js](double v) {
+    if (std::isnan(v)) js << "NaN";
+    else if (std::isinf(v)) js << (v > 0 ? "Infinity" : "-Infinity");
+    else js << v;
+  };
+  js << "[";
+  for (int f = 0; f < d->num_features(); ++f) {
+    const BinMapper* m = d->FeatureBinMapper(f);
+    const bool cat = m->bin_type() == BinType::Categorical;
+    js << (f > 0 ? ", " : "") << "{\"inner\": " << f << ", \"real\": " << d->RealFeatureIndex(f)
+       << ", \"num_bin\": " << m->num_bin() << ", \"missing_type\": " << static_cast<int>(m->missing_type())
+       << ", \"default_bin\": " << m->GetDefaultBin() << ", \"most_freq_bin\": " << m->GetMostFreqBin()
+       << ", \"offset\": " << (m->GetMostFreqBin() == 0 ? 1 : 0) << ", \"categorical\": " << (cat ? 1 : 0)
+       << ", \"group\": " << d->Feature2Group(f) << ", \"sub_feature\": " << d->Feature2SubFeature(f)
+       << ", \"group_offset\": " << d->group(d->Feature2Group(f)).bin_offsets[d->Feature2SubFeature(f)]
+       << ", \"hist_offset\": " << d->FeatureHistOffset(f) << ", \"hist_size\": " << d->FeatureHistSize(f)
+       << (cat ? ", \"categories\": [" : ", \"upper_bounds\": [");
+    for (int b = 0; b < m->num_bin(); ++b) {
+      if (b > 0) js << ", ";
+      if (cat) js << m->bin_2_categorical()[b];
+      else num(m->upper_bounds()[b]);
+    }
+    js << "]}";
+  }
+  js << "]";
+  const std::string rep = js.str();
+  *out_len = static_cast<int64_t>(rep.size()) + 1;
+  if (buffer_len >= *out_len) std::memcpy(out_str, rep.c_str(), rep.size() + 1);
   API_END();
 }
 

@@ -206,9 +206,9 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(NT == kWave 
     L.sg = cl.sum_g;
     L.sh = cl.sum_h + 2 * kEpsilon;
     L.n = lr == 0 ? lc : rc;
-    L.parent_out = cl.output;
     L.c.min = cl.cmin;
     L.c.max = cl.cmax;
+    L.parent_out = ScanParentOutput(cl.leaf == 0, cl.output, cl.sum_g, cl.sum_h, L.n, L.c, p);
     if (vote_local) {
       // this rank's rows of the child: the histogrammed child's sums from k_round_split, the
       // other one's as the parent's minus those (loaded here only: the extra loads in the

@@ -1082,7 +1082,7 @@ __device__ void RoundPlanBody(const KArgs& a, unsigned char* plan_lds) {
       lc.global_count = lcnt;
       lc.depth = depth;
       lc.slot = hl ? e.slot_new : P.st.slot;
-      lc.leaf = -1;
+      lc.leaf = P.st.leaf == 0 ? 0 : -1;  // (ids come with the replay; leaf 0 is the all-left path: ScanParentOutput)
       lc.frow = e.frow_child[0];
       lc.icmask = icm;
       rc.sum_g = rsg;

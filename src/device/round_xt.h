@@ -25,9 +25,9 @@ __device__ bool XtEvalNum(const KArgs& a, const Feature& F, int f, int node, con
   L.sg = cs.sum_g;
   L.sh = cs.sum_h + 2 * kEpsilon;
   L.n = n;
-  L.parent_out = cs.output;
   L.c.min = cs.cmin;
   L.c.max = cs.cmax;
+  L.parent_out = ScanParentOutput(cs.leaf == 0, cs.output, cs.sum_g, cs.sum_h, n, L.c, p);
   L.cnt_factor = L.n / L.sh;
   L.min_gain_shift = LeafGain(L.sg, L.sh, p.lambda_l1, p.lambda_l2, p.max_delta_step, p.path_smooth, L.n, L.parent_out,
                               p.use_l1, p.use_max_output, p.use_smoothing) +

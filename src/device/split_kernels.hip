@@ -389,9 +389,9 @@ __device__ __forceinline__ void FindBody(const KArgs& a, double* s_bins, FindSha
     L.sg = cl.sum_g;
     L.sh = cl.sum_h + 2 * kEpsilon;
     L.n = sd.global_count;
-    L.parent_out = cl.output;
     L.c.min = cl.cmin;
     L.c.max = cl.cmax;
+    L.parent_out = ScanParentOutput(sd.leaf == 0, cl.output, cl.sum_g, cl.sum_h, L.n, L.c, p);
     depth = cl.depth;
     slot = sd.slot;
     if (a.p.vote_phase == 1) {

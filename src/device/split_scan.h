@@ -77,6 +77,17 @@ struct LeafCtx {
   ConstraintRange c;
 };
 
+// the output a leaf's scan smooths towards (path_smooth): the one its parent's split gave it -- but for
+// leaf 0, the root and whichever leaf keeps its id, the leaf's own output with L1 and max_delta_step,
+// clamped to its range and not smoothed: the reference decides by the leaf's index
+// (serial_tree_learner.cpp ComputeBestSplitForFeature), and so does the host learner (EvalFeature)
+__device__ __forceinline__ double ScanParentOutput(bool leaf0, double output, double sum_g, double sum_h, int n,
+                                                   const ConstraintRange& c, const SplitParams& p) {
+  if (!leaf0 || !p.use_smoothing) return output;  // (read by nothing without smoothing)
+  const double r = LeafOutputRaw(sum_g, sum_h, p.lambda_l1, p.lambda_l2, p.max_delta_step, 0.0, n, 0.0, 1, 1, 0);
+  return r < c.min ? c.min : (r > c.max ? c.max : r);
+}
+
 // block-wide scans / reductions of the split scan (NT threads: kFindThreads, or one wave per
 // workgroup for narrow features); every thread calls them, results are returned to every thread
 template <int NT>

@@ -56,6 +56,7 @@ void GPUTreeLearner::AllocRoundState() {
     HIPCHECK(hipHostMalloc(reinterpret_cast<void**>(&h_round_), sizeof(dev::Round), hipHostMallocDefault));
   }
   if (h_tree_out_ != nullptr) (void)hipHostFree(h_tree_out_);
+  last_num_splits_ = 0;
   HIPCHECK(hipHostMalloc(reinterpret_cast<void**>(&h_tree_out_),
                          sizeof(int32_t) * dev::kHostOutHeaderWords +
                              sizeof(dev::SplitRecord) * std::max(1, config_->num_leaves - 1),

@@ -31,16 +31,38 @@ std::string Num(double v) {
   return o.str();
 }
 // whether the split that created `leaf` histogrammed / scanned its children: not for the
-// tree's last split, nor when both children are too small to split or at max_depth (the
+// last split of a full tree, nor when both children are too small to split or at max_depth (the
 // skip rule of StepChildren in src/device/device_common.h)
 bool LeafScanned(const Tree* tree, int leaf, const Config& cfg) {
   if (tree->num_leaves() <= 1) return true;
   const int p = tree->leaf_parent(leaf);
-  if (p == tree->num_leaves() - 2) return false;
+  // (a tree that stopped short of num_leaves did scan them: that is how it knew to stop)
+  if (p == tree->num_leaves() - 2 && tree->num_leaves() >= cfg.num_leaves) return false;
   const int sib = tree->left_child(p) == ~leaf ? tree->right_child(p) : tree->left_child(p);
   const int md = cfg.min_data_in_leaf;
   if (tree->leaf_count(leaf) < 2 * md && tree->data_count(sib) < 2 * md) return false;
   return !(cfg.max_depth > 0 && tree->leaf_depth(leaf) >= cfg.max_depth);
+}
+// a device best-split record as JSON fields: "feature": -1 alone when there is none
+void WriteSplit(const DeviceSplit& d, std::ostringstream* out) {
+  std::ostringstream& o = *out;
+  o << "\"feature\": " << d.feature;
+  if (d.feature < 0) return;
+  o << ", \"threshold\": " << d.threshold << ", \"gain\": " << Num(d.gain) << ", \"default_left\": "
+    << (d.default_left != 0 ? 1 : 0) << ", \"is_categorical\": " << (d.is_categorical != 0 ? 1 : 0)
+    << ", \"left_count\": " << d.left_count << ", \"right_count\": " << d.right_count
+    << ", \"left_sum_gradient\": " << Num(d.left_sum_gradient) << ", \"left_sum_hessian\": "
+    << Num(d.left_sum_hessian) << ", \"right_sum_gradient\": " << Num(d.right_sum_gradient)
+    << ", \"right_sum_hessian\": " << Num(d.right_sum_hessian) << ", \"left_output\": " << Num(d.left_output)
+    << ", \"right_output\": " << Num(d.right_output) << ", \"cat_bins\": [";
+  bool first = true;
+  for (int b = 0; d.is_categorical != 0 && b < 32 * kMaxCatWords; ++b) {
+    if ((d.cat_bits[b >> 5] >> (b & 31)) & 1u) {
+      o << (first ? "" : ", ") << b;
+      first = false;
+    }
+  }
+  o << "]";
 }
 }  // namespace
 
@@ -118,7 +140,16 @@ std::string GPUTreeLearner::DebugCheckSplits(const Tree* tree) {
   std::vector<hist_t> fh;
   int checked = 0, mismatched = 0, gain_mismatch = 0, direction_ties = 0;
   double max_rel = 0.0;
-  std::ostringstream details;
+  // the splits the tree was built from, in the order applied: the device record each scan's winner
+  // left, with the leaf it split (records: the leaves of the finished tree, whose winners were not applied)
+  std::ostringstream details, records, applied;
+  const dev::SplitRecord* recs =
+      last_recs_in_tree_out_ ? reinterpret_cast<const dev::SplitRecord*>(h_tree_out_ + dev::kHostOutHeaderWords) : h_rec_;
+  for (int k = 0; recs != nullptr && k < last_num_splits_ && k < L - 1; ++k) {
+    applied << (k > 0 ? ", " : "") << "{\"leaf\": " << recs[k].leaf << ", ";
+    WriteSplit(recs[k].split, &applied);
+    applied << "}";
+  }
   for (int l = 0; l < L; ++l) {
     const dev::Leaf& lf = leaves[l];
     if (!LeafScanned(tree, l, *config_)) continue;  // no split is evaluated
@@ -127,7 +158,7 @@ std::string GPUTreeLearner::DebugCheckSplits(const Tree* tree) {
     c.min = lf.cmin;
     c.max = lf.cmax;
     double parent_output = lf.output;
-    if (l == 0 && tree->num_leaves() == 1) {
+    if (l == 0) {  // (leaf 0 smooths towards its own unsmoothed output: ScanParentOutput in split_scan.h)
       SplitParams rp = params_;
       rp.use_l1 = 1;
       rp.use_max_output = 1;
@@ -163,6 +194,13 @@ std::string GPUTreeLearner::DebugCheckSplits(const Tree* tree) {
       if (ns > host_best) host_best = ns;
     }
     const DeviceSplit& d = best[l];
+    // the device's own record and what the scan was given, for a finder outside this library
+    // (tests/helpers/split_ref.py) to be run against
+    records << (checked > 0 ? ", " : "") << "{\"leaf\": " << l << ", ";
+    WriteSplit(d, &records);
+    records << ", \"sum_g\": " << Num(lf.sum_g) << ", \"sum_h\": " << Num(lf.sum_h) << ", \"num_data\": "
+            << lf.global_count << ", \"cmin\": " << Num(c.min) << ", \"cmax\": " << Num(c.max)
+            << ", \"parent_output\": " << Num(parent_output) << ", \"depth\": " << lf.depth << "}";
     if (d.feature < 0 && !(host_best.gain > 0 && std::isfinite(host_best.gain))) {
       ++checked;  // neither side found a split
       continue;
@@ -201,7 +239,8 @@ std::string GPUTreeLearner::DebugCheckSplits(const Tree* tree) {
      << mismatched << ", \"gain_mismatch\": " << gain_mismatch << ", \"direction_ties\": " << direction_ties
      << ", \"max_rel_gain_diff\": " << Num(max_rel) << ", \"layout\": \""
      << (sparse_rows_ ? "sparse" : args_.nibbles ? "4" : (args_.bin_bytes == 1 ? "8" : (args_.bin_bytes == 2 ? "16" : "mixed")))
-     << "\", \"hist_tiles\": " << args_.hist_tiles << ", \"details\": [" << details.str() << "]}";
+     << "\", \"hist_tiles\": " << args_.hist_tiles << ", \"details\": [" << details.str() << "], \"records\": ["
+     << records.str() << "], \"applied\": [" << applied.str() << "]}";
   return js.str();
 }
 

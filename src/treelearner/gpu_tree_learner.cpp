@@ -65,6 +65,7 @@ void GPUTreeLearner::FreeBuffers() {
     if (*hp) (void)hipHostFree(*hp);
     *hp = nullptr;
   }
+  last_num_splits_ = 0;
   d_score_ = nullptr;
   d_grad_ = d_hess_ = nullptr;
   d_label_ = d_weights_ = d_label_weight_ = nullptr;
@@ -753,6 +754,7 @@ void GPUTreeLearner::ResetConfig(const Config* config) {
     d_hist_ = Alloc<long long>(static_cast<size_t>(hist_slots_) * 2 * total_bins_);
     d_leaf_values_ = Alloc<double>(n_leaves);
     if (h_rec_) (void)hipHostFree(h_rec_);
+    last_num_splits_ = 0;
     HIPCHECK(hipHostMalloc(reinterpret_cast<void**>(&h_rec_), sizeof(dev::SplitRecord) * std::max(1, n_leaves - 1),
                            hipHostMallocDefault));
     args_.p.num_leaves = n_leaves;
@@ -1221,6 +1223,8 @@ Tree* GPUTreeLearner::TrainDeviceMode(bool speculated) {
   }
   if (copy_recs) HIPCHECK(hipEventSynchronize(rec_event_));
   std::unique_ptr<Tree> tree(TreeFromRecords(recs, num_splits));
+  last_num_splits_ = num_splits;
+  last_recs_in_tree_out_ = rounds && tree_out_used_;
   // the records are consumed: the next tree may be launched now (its last plan rewrites them)
   const bool spec_ok = rounds && SpeculationEligible() && early_scored_leaves_ == num_splits + 1 && num_splits >= 1;
   Log::Debug("device learner: next tree %s (allowed %d, rounds %d, scored early %d/%d)", spec_ok ? "launched" : "not launched",

@@ -500,6 +500,11 @@ class GPUTreeLearner : public SerialTreeLearner, public DeviceTreeLearner {
   // pinned host staging
   int8_t* h_mask_ = nullptr;
   dev::SplitRecord* h_rec_ = nullptr;
+  // how many records the last device-grown tree was built from and which pinned buffer holds them
+  // (h_rec_, or h_tree_out_ past its header); 0 again wherever either buffer is freed.  Read by
+  // DebugCheckSplits only
+  int last_num_splits_ = 0;
+  bool last_recs_in_tree_out_ = false;
   dev::Step* h_step_ = nullptr;
   double* h_root_ = nullptr;
   // sizes

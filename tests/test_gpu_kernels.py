@@ -12,6 +12,11 @@ tree leaves in HBM (read back through LGBM_AMD_BoosterDevice* in the C API):
   values, most-frequent-bin offset, categorical (one-hot and sorted), monotone, L1 /
   max_delta_step / path smoothing, wide int64 histograms (gpu_use_dp), bagging, EFB bundles,
   and multi-block leaves (> 16k rows).
+
+The scans see here whatever trained random data reaches, and are held to the project's own host
+finder.  The edges this does not reach -- 65..2049 stored bins, the special bins placed on purpose,
+limits, exact ties -- and a finder written apart from the library are in
+tests/test_device_split_ref.py (tests/helpers/split_ref.py, tests/helpers/split_cases.py).
 """
 import ctypes
 import json
