@@ -5,27 +5,19 @@
 namespace lgbm_amd {
 namespace dev {
 
-#ifndef LGBM_FIND_WAVE_OCC
-#define LGBM_FIND_WAVE_OCC 2  // (one-wave scans without register spills: see split_kernels.hip)
-#endif
-
 // ----------------------------------------------------------------------------- k_round_find
 template <int KIND, int NT>
 struct RoundFindShared {
-  BlockScratch<NT> sc;
-  ScanScratch<NT> ssc;
-  Cand sc2[NT / kWave];
-  typename std::conditional<KIND == 2, CatScratchT<kFindCatNarrow>,
-                            typename std::conditional<KIND == 3, CatScratchT<kFindMaxCatBins>, int>::type>::type cat_sc;
-  unsigned long long s_red[2 * NT];
-  ArgC arg[NT / kWave];
+  ScanShared<KIND, NT> scan;
+  ArgC arg[NT / kWave];  // ChildBest's per-wave winners
 };
 
 // the best split of child y (2j + lr) of the round, node `node`, from its per-feature
 // results, by the child's last split-scan workgroup (SplitInfo order: larger gain, then
 // smaller real feature)
+// (inline: as RoundPlanBody)
 template <int KIND, int NT>
-__device__ void ChildBest(const KArgs& a, int y, int node, RoundFindShared<KIND, NT>& sh) {
+__device__ inline void ChildBest(const KArgs& a, int y, int node, RoundFindShared<KIND, NT>& sh) {
   const int NF = a.p.num_features, tid = threadIdx.x;
   const FeatureBest* fb0 = a.feat_best;
   constexpr int kB = 8;
@@ -72,10 +64,7 @@ __device__ void ChildBest(const KArgs& a, int y, int node, RoundFindShared<KIND,
         PublishCatCopy(a.cbest_cat + ci * kMaxCatWords, a.feat_cat + wi * kMaxCatWords);
       }
     } else {
-      FeatureBest none = {};
-      none.gain = -INFINITY;
-      none.feature = none.real_feature = -1;
-      PublishRecord(dst, none);
+      PublishRecord(dst, FeatureBestNone());
     }
   }
 }
@@ -175,18 +164,7 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(NT == kWave 
   FeatureBest* fb_out = &a.feat_best[RoundFbIndex(a, y, f)];
   int8_t* flags = a.splittable + static_cast<size_t>(frow) * NF;
   const SplitParams& p = a.p.sp;
-  FeatureBest o;
-  o.gain = -INFINITY;
-  o.feature = -1;
-  o.real_feature = -1;
-  o.thr = 0;
-  o.default_left = 1;
-  o.lc = o.rc = 0;
-  o.mono = 0;
-  o.ncat = 0;
-  o.flag = -1;
-  o.pad = 0;
-  o.lg = o.lh = o.rg = o.rh = o.lo = o.ro = 0.0;
+  FeatureBest o = FeatureBestEmpty();
   bool write = true;
   if (KIND == 1 && F.is_cat) {
     write = false;  // the categorical kernel scans it
@@ -230,96 +208,20 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(NT == kWave 
     const size_t pstride = static_cast<size_t>(units) * a.p.total_bins;
     const unsigned long long* part = a.partials + static_cast<size_t>(blk_off) * pstride + static_cast<size_t>(units) * F.hist_offset;
     const bool stage = a.p.max_feature_bins <= kFindLdsBins;
-    double* sgv = s_bins;
+    double* sg = s_bins;
     double* shv = s_bins + (stage ? a.p.max_feature_bins : 0);
     const bool subtract = !is_hist && !vote_global;
     const int nblk_direct = (!owner && !vote_global && nblk <= kDirectChunk) ? nblk : -1;
-    const bool spread = nblk_direct > 1 && 2 * nbf <= NT;
-    long long pg0 = 0, ph0 = 0;
-    if (subtract && tid < nbf) {
-      pg0 = dst[2 * tid];
-      ph0 = dst[2 * tid + 1];
-    }
-    if (spread) {
-      for (int i = tid; i < 2 * nbf; i += NT) sh.s_red[i] = 0ull;
-      __syncthreads();
-      const int per = NT / nbf;
-      const int i = tid % nbf, r = tid / nbf;
-      if (r < per) {
-        constexpr int kC = 8;
-        long long g = 0, h = 0;
-        for (int k0 = r; k0 < nblk_direct; k0 += per * kC) {
-          unsigned long long v0[kC], v1[kC];
-#pragma unroll
-          for (int cc = 0; cc < kC; ++cc) {
-            const int k = k0 + cc * per;
-            const unsigned long long* q = part + k * pstride + static_cast<size_t>(units) * i;
-            v0[cc] = k < nblk_direct ? q[0] : 0ull;
-            v1[cc] = (k < nblk_direct && units == 2) ? q[1] : 0ull;
-          }
-#pragma unroll
-          for (int cc = 0; cc < kC; ++cc) {
-            long long pgv, phv;
-            UnpackPartial(v0[cc], v1[cc], units, &pgv, &phv);
-            g += pgv;
-            h += phv;
-          }
-        }
-        atomicAdd(&sh.s_red[2 * i], static_cast<unsigned long long>(g));
-        atomicAdd(&sh.s_red[2 * i + 1], static_cast<unsigned long long>(h));
-      }
-      __syncthreads();
-    }
-    for (int i = tid; i < nbf; i += NT) {
-      long long g = 0, h = 0;
-      if (spread) {
-        g = static_cast<long long>(sh.s_red[2 * i]);
-        h = static_cast<long long>(sh.s_red[2 * i + 1]);
-      } else if (nblk_direct >= 0) {
-        for (int k0 = 0; k0 < nblk_direct; k0 += kDirectChunk) {
-          unsigned long long v0[kDirectChunk], v1[kDirectChunk];
-#pragma unroll
-          for (int k = 0; k < kDirectChunk; ++k) {
-            const unsigned long long* q = part + (k0 + k) * pstride + static_cast<size_t>(units) * i;
-            v0[k] = k0 + k < nblk_direct ? q[0] : 0ull;
-            v1[k] = (k0 + k < nblk_direct && units == 2) ? q[1] : 0ull;
-          }
-#pragma unroll
-          for (int k = 0; k < kDirectChunk; ++k) {
-            long long pgv, phv;
-            UnpackPartial(v0[k], v1[k], units, &pgv, &phv);
-            g += pgv;
-            h += phv;
-          }
-        }
-      } else {
-        g = src[2 * i];
-        h = src[2 * i + 1];
-      }
-      if (subtract) {
-        g = (i == tid ? pg0 : dst[2 * i]) - g;
-        h = (i == tid ? ph0 : dst[2 * i + 1]) - h;
-      }
-      if (!vote_global) {
-        dst[2 * i] = g;
-        dst[2 * i + 1] = h;
-      }
-      if (stage) {
-        sgv[i] = static_cast<double>(g) * ig;
-        shv[i] = static_cast<double>(h) * ih;
-      }
-    }
-    __syncthreads();
+    // (the voting global scan reads the all-reduced bins in place and stores nothing back)
+    StageHistogram<NT, !VG>(dst, src, part, pstride, units, nbf, nblk_direct, subtract, ig, ih, stage, sg, shv,
+                            sh.scan.s_red);
     if (ktw) kt[2] = wall_clock64();
     if (used) {
-      L.cnt_factor = L.n / L.sh;
-      const double gain_shift = LeafGain(L.sg, L.sh, p.lambda_l1, p.lambda_l2, p.max_delta_step, p.path_smooth, L.n,
-                                         L.parent_out, p.use_l1, p.use_max_output, p.use_smoothing);
-      L.min_gain_shift = gain_shift + p.min_gain_to_split;
+      FinishLeafCtx(&L, p);
       o.feature = f;
       o.real_feature = F.real_index;
       HistView hv;
-      hv.lg = stage ? sgv : nullptr;
+      hv.lg = stage ? sg : nullptr;
       hv.lh = stage ? shv : nullptr;
       hv.h = dst;
       hv.inv_g = ig;
@@ -327,15 +229,16 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(NT == kWave 
       bool splittable;
       if constexpr (!CAT) {
         if (a.round_xt) {  // (extra_trees: the prefixes the replay evaluates its drawn thresholds from)
-          XtStorePrefix<NT>(F, hv, L, a.node_pre + static_cast<size_t>(frow) * a.p.total_bins + F.hist_offset, &sh.ssc);
+          XtStorePrefix<NT>(F, hv, L, a.node_pre + static_cast<size_t>(frow) * a.p.total_bins + F.hist_offset,
+                            &sh.scan.ssc);
         }
       }
       if constexpr (CAT) {
         splittable = FindCategoricalBlock(F, hv, L, p, &o, a.feat_cat + RoundFbIndex(a, y, f) * kMaxCatWords,
-                                          &sh.sc, &sh.cat_sc);
+                                          &sh.scan.sc, &sh.scan.cat_sc);
       } else {
-        splittable = FindNumericalBlock<SIMPLE, NT>(F, hv, L, p, cl.depth, a.p.monotone_penalty, &o, &sh.sc, &sh.ssc,
-                                                    sh.sc2, kNoRandThr);
+        splittable = FindNumericalBlock<SIMPLE, NT>(F, hv, L, p, cl.depth, a.p.monotone_penalty, &o, &sh.scan.sc,
+                                                    &sh.scan.ssc, sh.scan.sc2, kNoRandThr);
       }
       if (tid == 0 && !vote_global) {  // (voting: the local scan's flags; categorical: thread 0 decides)
         flags[f] = splittable ? 1 : 0;
@@ -344,9 +247,7 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(NT == kWave 
       // CEGB (GPUTreeLearner::CegbRounds: no refunds in a round tree), before the monotone
       // penalty as SerialTreeLearner::ComputeBestSplitForFeature
       if (a.p.cegb && !a.round_cegb) {  // (KArgs::round_cegb: the replay subtracts them)
-        double delta = a.p.cegb_split * L.n;
-        if (a.cegb_coupled != nullptr && !a.cegb_used[f]) delta += a.cegb_coupled[f];
-        o.gain -= delta;
+        o.gain -= CegbScanDelta(a, f, L.n);
       }
       if (!CAT && !SIMPLE && F.monotone != 0) o.gain *= MonotonePenalty(cl.depth, a.p.monotone_penalty);
       if (o.gain == -INFINITY) o.feature = -1;
@@ -412,22 +313,7 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(NT == kWave 
   if (!PIF || !a.plan_in_find) return;
   // the last child of the round to finish plans the next round (its scans' results were
   // published write-through; one agent-scope acquire)
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  ArrivalRelease();
-  __syncthreads();
-  if (tid == 0) {
-    const unsigned n = 2u * static_cast<unsigned>(nexp);
-    int last = 0;
-    if (atomicAdd(&rd->child_done, 1u) == n - 1) {
-      last = 1;
-      rd->child_done = 0u;
-      __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    }
-    s_last = last;
-  }
-  __syncthreads();
-  if (!s_last) return;
+  if (!LastOfCount(&rd->child_done, 2u * static_cast<unsigned>(nexp), &s_last)) return;
   if (ktw) {
     for (int k = 0; k < 6; ++k) a.ktrace[static_cast<size_t>(rround) * kTraceSlots + 26 + k] = kt[k];
 #if LGBM_FIND_PHASES
@@ -462,39 +348,17 @@ size_t RoundPlanLds(int num_leaves, int nodes) {
 
 namespace {
 
-bool RoundSimpleGains(const KArgs& a) {
-  const SplitParams& p = a.p.sp;
-  return !p.use_l1 && !p.use_max_output && !p.use_smoothing && !p.use_mc;
-}
-
 template <bool VG, bool PIF>
 void LaunchRoundFindT(const KArgs& a, hipStream_t s) {
   const int ny = 2 * a.round_k;
-  size_t lds = a.p.max_feature_bins <= kFindLdsBins ? 2 * sizeof(double) * static_cast<size_t>(a.p.max_feature_bins) : 0;
+  size_t lds = FindBinsLds(a);
   if (a.plan_in_find) lds = std::max(lds, RoundPlanLds(a.p.num_leaves, a.round_nodes));
-  const bool simple = RoundSimpleGains(a);
-  const bool narrow = a.p.max_feature_bins <= kWave;
-  const dim3 b(narrow ? kWave : kFindThreads), bc(kFindThreads);
   // (voting global scan: every elected slot, numerical or categorical, in both kernels)
   const int ncat = (a.round_vote && a.p.vote_phase == 2) ? a.num_scan : a.p.has_cat;
-  const dim3 gn(a.num_scan, ny);
-  if (a.p.has_cat) {
-    if (narrow) {
-      if (simple) hipLaunchKernelGGL((k_round_find<1, true, kWave, VG, PIF>), gn, b, lds, s, a);
-      else hipLaunchKernelGGL((k_round_find<1, false, kWave, VG, PIF>), gn, b, lds, s, a);
-    } else {
-      if (simple) hipLaunchKernelGGL((k_round_find<1, true, kFindThreads, VG, PIF>), gn, b, lds, s, a);
-      else hipLaunchKernelGGL((k_round_find<1, false, kFindThreads, VG, PIF>), gn, b, lds, s, a);
-    }
-    if (a.p.wide_cat) hipLaunchKernelGGL((k_round_find<3, false, kFindThreads, VG, PIF>), dim3(ncat, ny), bc, lds, s, a);
-    else hipLaunchKernelGGL((k_round_find<2, false, kFindThreads, VG, PIF>), dim3(ncat, ny), bc, lds, s, a);
-  } else if (narrow) {
-    if (simple) hipLaunchKernelGGL((k_round_find<0, true, kWave, VG, PIF>), gn, b, lds, s, a);
-    else hipLaunchKernelGGL((k_round_find<0, false, kWave, VG, PIF>), gn, b, lds, s, a);
-  } else {
-    if (simple) hipLaunchKernelGGL((k_round_find<0, true, kFindThreads, VG, PIF>), gn, b, lds, s, a);
-    else hipLaunchKernelGGL((k_round_find<0, false, kFindThreads, VG, PIF>), gn, b, lds, s, a);
-  }
+  DispatchScans(a, [&](auto kind, auto simple, auto nt) {
+    hipLaunchKernelGGL((k_round_find<kind(), simple(), nt(), VG, PIF>), dim3(kind() >= 2 ? ncat : a.num_scan, ny),
+                       dim3(nt()), lds, s, a);
+  });
 }
 
 void LaunchRoundFind(const KArgs& a, hipStream_t s) {
@@ -542,21 +406,7 @@ __global__ __launch_bounds__(kFindThreads) void k_round_childbest(KArgs a) {
       }
     }
   }
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  ArrivalRelease();
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    int last = 0;
-    if (atomicAdd(&rd->child_done, 1u) == gridDim.x - 1u) {
-      last = 1;
-      rd->child_done = 0u;
-      __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    }
-    s_last = last;
-  }
-  __syncthreads();
-  if (!s_last || done) return;
+  if (!LastOfCount(&rd->child_done, gridDim.x, &s_last) || done) return;
   RoundPlanBody<false, kFindThreads>(a, plan_lds);
 }
 

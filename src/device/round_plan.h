@@ -1,6 +1,7 @@
 // Round growth, the planner (round_common.h): replay, prediction and the next round's plans.
 #pragma once
 
+#include "find_stage.h"
 #include "round_common.h"
 #include "round_xt.h"
 
@@ -223,10 +224,7 @@ __device__ bool DeferAccept(const KArgs& a, int s, int w, int n, int c, int* dra
   const bool scanned = s + 1 < L - 1 && !(a.p.max_depth > 0 && depth >= a.p.max_depth) && !(nl < 2 * md && nr < 2 * md);
   if (!scanned) {
     if (lane < 2) {
-      FeatureBest none = {};
-      none.gain = -INFINITY;
-      none.feature = none.real_feature = -1;
-      a.cbest[c + lane] = none;
+      a.cbest[c + lane] = FeatureBestNone();
       ng[c + lane] = -INFINITY;
       nrf[c + lane] = -1;
       nfi[c + lane] = -1;
@@ -264,9 +262,7 @@ __device__ bool DeferAccept(const KArgs& a, int s, int w, int n, int c, int* dra
   // -- and the penalties of the model's used set now are subtracted here)
   auto cegb_take = [&](FeatureBest* o, int leaf, int f, int rows) {
     a.cegb_mem[static_cast<size_t>(leaf) * NF + f] = *o;
-    double delta = a.p.cegb_split * rows;
-    if (a.cegb_coupled != nullptr && !a.cegb_used[f]) delta += a.cegb_coupled[f];
-    o->gain -= delta;
+    o->gain -= CegbScanDelta(a, f, rows);
   };
   ArgC cs = ArgNone(), cl = ArgNone();
   FeatureBest rec_s, rec_l;  // (extra_trees: this lane's best records of the two children)
@@ -370,9 +366,7 @@ __device__ bool DeferAccept(const KArgs& a, int s, int w, int n, int c, int* dra
     }
   }
   const ArgC bcs = ArgWaveBest(cs), bcl = ArgWaveBest(cl);
-  FeatureBest none = {};
-  none.gain = -INFINITY;
-  none.feature = none.real_feature = -1;
+  const FeatureBest none = FeatureBestNone();
   if (xt) {
     // the lane holding a child's winner hands its record over through LDS; lanes 0 / 1 store
     // the children's bests (a uniform-address store from a lane picked at run time lost its
@@ -635,8 +629,11 @@ __device__ void HostTreeOut(const KArgs& a, int nsplit, int rounds, int nodes, i
   }
 }
 
+// (inline: the compiler refuses to inline an unhinted function into a caller once the two have
+// more than 1100 basic blocks together, which the categorical scans are within a few blocks of;
+// a called plan costs them a called function's register and stack budget)
 template <bool ROOT, int NT, bool XT = false>
-__device__ void RoundPlanBody(const KArgs& a, unsigned char* plan_lds) {
+__device__ inline void RoundPlanBody(const KArgs& a, unsigned char* plan_lds) {
   constexpr int kPlanThreads = NT;
   __shared__ int s_done, s_s1, s_nexp, s_draw;
   __shared__ ArgC s_arg[kPlanThreads / kWave];
@@ -707,9 +704,7 @@ __device__ void RoundPlanBody(const KArgs& a, unsigned char* plan_lds) {
     if (b.idx >= 0 && b.g == -INFINITY) b.idx = -1;
     if (tid == 0) {
       // node 0: the root leaf and its best split
-      FeatureBest fb = {};
-      fb.gain = -INFINITY;
-      fb.feature = fb.real_feature = -1;
+      FeatureBest fb = FeatureBestNone();
       if (b.idx >= 0) {
         fb = a.feat_best[FeatBestIndex(a, 0, b.idx)];
         const uint32_t* cat = FeatCat(a, 0, b.idx);

@@ -1,6 +1,7 @@
 // extra_trees on round growth: the replay's evaluation of a drawn threshold (round_plan.h)
 #pragma once
 
+#include "find_stage.h"
 #include "round_common.h"
 
 namespace lgbm_amd {
@@ -14,7 +15,7 @@ namespace dev {
 __device__ bool XtEvalNum(const KArgs& a, const Feature& F, int f, int node, const ChildStats& cs, int n, int rthr,
                           FeatureBest* out) {
   const SplitParams& p = a.p.sp;
-  const bool simple = !p.use_l1 && !p.use_max_output && !p.use_smoothing && !p.use_mc;
+  const bool simple = SimpleGains(p);
   const XtPre* pre = a.node_pre + static_cast<size_t>(node) * a.p.total_bins + F.hist_offset;
   const int nb = F.num_bin - F.offset, offset = F.offset;
   const bool two = F.num_bin > 2 && F.missing_type != 0;
@@ -28,10 +29,7 @@ __device__ bool XtEvalNum(const KArgs& a, const Feature& F, int f, int node, con
   L.c.min = cs.cmin;
   L.c.max = cs.cmax;
   L.parent_out = ScanParentOutput(cs.leaf == 0, cs.output, cs.sum_g, cs.sum_h, n, L.c, p);
-  L.cnt_factor = L.n / L.sh;
-  L.min_gain_shift = LeafGain(L.sg, L.sh, p.lambda_l1, p.lambda_l2, p.max_delta_step, p.path_smooth, L.n, L.parent_out,
-                              p.use_l1, p.use_max_output, p.use_smoothing) +
-                     p.min_gain_to_split;
+  FinishLeafCtx(&L, p);
   // the entries (one batch of loads): the last (every stored bin), the one before it (the NaN
   // bin), the default bin and the one before it (the default bin's own sums, taken out of every
   // prefix past it as the scan leaves it out), the reverse candidate's exclusive prefix and the
@@ -147,18 +145,11 @@ __device__ bool XtEvalNum(const KArgs& a, const Feature& F, int f, int node, con
       fb_lc = xc;
     }
   }
-  FeatureBest o;
-  o.gain = -INFINITY;
+  FeatureBest o = FeatureBestEmpty();
   o.feature = f;
   o.real_feature = F.real_index;
-  o.thr = 0;
   o.default_left = two ? 1 : (F.missing_type == 2 ? 0 : 1);
-  o.lc = o.rc = 0;
   o.mono = F.monotone;
-  o.ncat = 0;
-  o.flag = -1;
-  o.pad = 0;
-  o.lg = o.lh = o.rg = o.rh = o.lo = o.ro = 0.0;
   for (int d = 0; d < (two ? 2 : 1); ++d) {
     const double bg = d == 0 ? rb_gain : fb_gain;
     if (any && bg > o.gain + L.min_gain_shift) {

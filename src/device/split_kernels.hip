@@ -14,7 +14,7 @@
 // go to feat_best.  The last workgroup of the step to finish (a device-scope counter) then
 // records the step and picks the next split (pick.h), so the next k_split starts from one
 // small Step record.
-#include "split_scan.h"
+#include "find_stage.h"
 
 namespace lgbm_amd {
 namespace dev {
@@ -142,10 +142,7 @@ __device__ void ForcedGather(const Feature& F, HistView hv, const LeafCtx& L, co
   const double gain_shift = LeafGainGivenOutput(sum_g, sum_h, p.lambda_l1, p.lambda_l2, L.parent_out, 1);
   const double min_gain_shift = gain_shift + p.min_gain_to_split;
   const double cnt_factor = L.n / sum_h;
-  FeatureBest o = {};
-  o.gain = -INFINITY;
-  o.feature = -1;
-  o.real_feature = -1;
+  FeatureBest o = FeatureBestNone();
   *cat_bin = -1;  // (the forced category: the set published by the caller)
   double lg, lh, rg, rh;
   int lc, rc;
@@ -206,22 +203,12 @@ __device__ void ForcedGather(const Feature& F, HistView hv, const LeafCtx& L, co
   *out = o;
 }
 
-template <bool ROOT, int KIND, int NT>
-struct FindShared {
-  BlockScratch<NT> sc;
-  ScanScratch<NT> ssc;
-  Cand sc2[NT / kWave];
-  typename std::conditional<KIND == 2, CatScratchT<kFindCatNarrow>,
-                            typename std::conditional<KIND == 3, CatScratchT<kFindMaxCatBins>, int>::type>::type cat_sc;
-  unsigned long long s_red[2 * NT];  // direct partial sums of narrow features
-};
-
 // the scan of one (feature, child) by one workgroup: every thread of the workgroup takes the
 // same path (the kernel's pick tail needs all of them)
 // side: the child (0: the smaller one); d0_in / drew: categorical extra_trees only -- the draws
 // the smaller child's scan of this feature consumed, and this scan's (see k_find)
 template <bool ROOT, int KIND, bool SIMPLE, int NT>
-__device__ __forceinline__ void FindBody(const KArgs& a, double* s_bins, FindShared<ROOT, KIND, NT>& sh, const int side,
+__device__ __forceinline__ void FindBody(const KArgs& a, double* s_bins, ScanShared<KIND, NT>& sh, const int side,
                                          const int d0_in, int* drew) {
   if (drew != nullptr) *drew = 0;
   constexpr bool CAT = KIND >= 2;  // (3: the wide categorical variant)
@@ -441,31 +428,14 @@ __device__ __forceinline__ void FindBody(const KArgs& a, double* s_bins, FindSha
     // the parent could not split on f: neither child evaluates it, the smaller child's row
     // says so and the larger child keeps the parent's row (SerialTreeLearner::FindBestSplits)
     if (side == 0 && tid == 0) flags[f] = 0;
-    if (tid == 0) {
-      FeatureBest none = {};
-      none.gain = -INFINITY;
-      none.feature = none.real_feature = -1;
-      PublishRecord(fb_out, none);
-    }
+    if (tid == 0) PublishRecord(fb_out, FeatureBestNone());
     return;
   }
-  L.cnt_factor = L.n / L.sh;
-  const double gain_shift = LeafGain(L.sg, L.sh, p.lambda_l1, p.lambda_l2, p.max_delta_step, p.path_smooth, L.n,
-                                     L.parent_out, p.use_l1, p.use_max_output, p.use_smoothing);
-  L.min_gain_shift = gain_shift + p.min_gain_to_split;
+  FinishLeafCtx(&L, p);
 
-  FeatureBest o;
-  o.gain = -INFINITY;
+  FeatureBest o = FeatureBestEmpty();
   o.feature = f;
   o.real_feature = F.real_index;
-  o.thr = 0;
-  o.default_left = 1;
-  o.lc = o.rc = 0;
-  o.mono = 0;
-  o.ncat = 0;
-  o.flag = -1;
-  o.pad = 0;
-  o.lg = o.lh = o.rg = o.rh = o.lo = o.ro = 0.0;
   // a sampled-out feature (bynode) still materialises its histogram: descendants subtract it
   if (tree_used && (!F.is_cat || F.num_bin <= kFindMaxCatBins)) {
     const int nh = 2 * a.p.total_bins;
@@ -482,87 +452,8 @@ __device__ __forceinline__ void FindBody(const KArgs& a, double* s_bins, FindSha
     double* sg = s_bins;
     double* shv = s_bins + (stage ? a.p.max_feature_bins : 0);
     const bool subtract = !ROOT && !sd.is_hist && !vote_global;  // parent - the histogrammed child, in place
-    // a feature with fewer bins than threads sums its direct partials with every thread:
-    // kFindThreads / nbf threads per bin stride over the row blocks, then combine in LDS
-    // (one thread per bin walking hundreds of partials would be a chain of round trips)
-    const bool spread = nblk_direct > 1 && 2 * nbf <= kFindThreads;
-    // the parent's bins (first bin of each thread): loaded up front, so their round trip
-    // overlaps the partial-sum loads instead of following them
-    long long pg0 = 0, ph0 = 0;
-    if (subtract && tid < nbf) {
-      pg0 = dst[2 * tid];
-      ph0 = dst[2 * tid + 1];
-    }
-    if (spread) {
-      for (int j = tid; j < 2 * nbf; j += kFindThreads) sh.s_red[j] = 0ull;
-      __syncthreads();
-      const int per = kFindThreads / nbf;
-      const int i = tid % nbf, r = tid / nbf;
-      if (r < per) {
-        constexpr int kC = 8;
-        long long g = 0, h = 0;
-        for (int k0 = r; k0 < nblk_direct; k0 += per * kC) {
-          unsigned long long v0[kC], v1[kC];
-#pragma unroll
-          for (int cc = 0; cc < kC; ++cc) {
-            const int k = k0 + cc * per;
-            const unsigned long long* q = part + k * pstride + static_cast<size_t>(units) * i;
-            v0[cc] = k < nblk_direct ? q[0] : 0ull;
-            v1[cc] = (k < nblk_direct && units == 2) ? q[1] : 0ull;
-          }
-#pragma unroll
-          for (int cc = 0; cc < kC; ++cc) {
-            long long pgv, phv;
-            UnpackPartial(v0[cc], v1[cc], units, &pgv, &phv);
-            g += pgv;
-            h += phv;
-          }
-        }
-        atomicAdd(&sh.s_red[2 * i], static_cast<unsigned long long>(g));
-        atomicAdd(&sh.s_red[2 * i + 1], static_cast<unsigned long long>(h));
-      }
-      __syncthreads();
-    }
-    for (int i = tid; i < nbf; i += kFindThreads) {
-      long long g = 0, h = 0;
-      if (spread) {
-        g = static_cast<long long>(sh.s_red[2 * i]);
-        h = static_cast<long long>(sh.s_red[2 * i + 1]);
-      } else if (nblk_direct >= 0) {
-        // small leaf: sum the few per-block partials here (k_hist_reduce skipped them),
-        // chunks of kDirectChunk independent loads in flight
-        for (int k0 = 0; k0 < nblk_direct; k0 += kDirectChunk) {
-          unsigned long long v0[kDirectChunk], v1[kDirectChunk];
-#pragma unroll
-          for (int k = 0; k < kDirectChunk; ++k) {
-            const unsigned long long* q = part + (k0 + k) * pstride + static_cast<size_t>(units) * i;
-            v0[k] = k0 + k < nblk_direct ? q[0] : 0ull;
-            v1[k] = (k0 + k < nblk_direct && units == 2) ? q[1] : 0ull;
-          }
-#pragma unroll
-          for (int k = 0; k < kDirectChunk; ++k) {
-            long long pgv, phv;
-            UnpackPartial(v0[k], v1[k], units, &pgv, &phv);
-            g += pgv;
-            h += phv;
-          }
-        }
-      } else {
-        g = src[2 * i];
-        h = src[2 * i + 1];
-      }
-      if (subtract) {
-        g = (i == tid ? pg0 : dst[2 * i]) - g;
-        h = (i == tid ? ph0 : dst[2 * i + 1]) - h;
-      }
-      dst[2 * i] = g;
-      dst[2 * i + 1] = h;
-      if (stage) {
-        sg[i] = static_cast<double>(g) * ig;
-        shv[i] = static_cast<double>(h) * ih;
-      }
-    }
-    __syncthreads();  // the workgroup's stores become visible to all its threads
+    StageHistogram<NT, true>(dst, src, part, pstride, units, nbf, nblk_direct, subtract, ig, ih, stage, sg, shv,
+                             sh.s_red);
     if (!ROOT) KTrace(a, s, kTrFindLoaded);
     // voting extra_trees: the reference's local scans skip the features the parent's local scan
     // could not split (at its random threshold) -- their histograms exist for the vote, they
@@ -571,10 +462,7 @@ __device__ __forceinline__ void FindBody(const KArgs& a, double* s_bins, FindSha
     if (!used || vote_skip) {
       if (tid == 0) {
         if (vote_skip) flags[f] = 0;
-        FeatureBest none = {};
-        none.gain = -INFINITY;
-        none.feature = none.real_feature = -1;
-        PublishRecord(fb_out, none);
+        PublishRecord(fb_out, FeatureBestNone());
       }
       return;
     }
@@ -608,8 +496,7 @@ __device__ __forceinline__ void FindBody(const KArgs& a, double* s_bins, FindSha
           PublishCatCopy(a.cegb_mem_cat + mi * kMaxCatWords, a.feat_cat + FeatBestIndex(a, side, f) * kMaxCatWords);
         }
       }
-      double delta = a.p.cegb_split * L.n;
-      if (a.cegb_coupled != nullptr && !a.cegb_used[f]) delta += a.cegb_coupled[f];
+      double delta = CegbScanDelta(a, f, L.n);
       if (a.cegb_lazy != nullptr) delta += a.cegb_lazy[f] * static_cast<double>(unpaid);
       o.gain -= delta;
     }
@@ -638,13 +525,6 @@ __device__ __forceinline__ void FindBody(const KArgs& a, double* s_bins, FindSha
   if (tid == 0) PublishRecord(fb_out, o);
 }
 
-#ifndef LGBM_FIND_WAVE_OCC
-// one-wave split scans: waves per SIMD the register budget allows.  2 (256 VGPRs): at 4 the
-// non-root kernels spilled 72-76 bytes per lane, and trees grown with them changed with
-// unrelated code edits (one-split-per-step categorical trees, voting ranks that disagreed)
-// while the spill-free build stayed exact -- tests/test_gpu_distributed.py voting cases
-#define LGBM_FIND_WAVE_OCC 2
-#endif
 constexpr unsigned kFindFlatMax = 128;  // split-scan grids up to this size count arrivals on one counter
 
 // NT: threads per workgroup -- kFindThreads, or one wave (kWave) when every feature has at
@@ -653,7 +533,7 @@ constexpr unsigned kFindFlatMax = 128;  // split-scan grids up to this size coun
 template <bool ROOT, int KIND, bool SIMPLE, int NT>
 __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(NT == kWave ? LGBM_FIND_WAVE_OCC : 1))) void k_find(KArgs a) {
   extern __shared__ double s_bins[];  // [2][max_feature_bins] dequantised (g, h), if they fit
-  __shared__ FindShared<ROOT, KIND, NT> sh;
+  __shared__ ScanShared<KIND, NT> sh;
   __shared__ PickLds pl;
   __shared__ int s_last;
   Step* st = a.st;
@@ -735,43 +615,20 @@ __global__ __launch_bounds__(kFindThreads) void k_pick(KArgs a, int root) {
 }
 
 static size_t FindLds(const KArgs& a) {
-  const size_t bins = a.p.max_feature_bins <= kFindLdsBins ? 2 * sizeof(double) * static_cast<size_t>(a.p.max_feature_bins) : 0;
   // intermediate monotone: the picking workgroup walks the tree in this LDS (MonoInterLds)
-  return a.p.mono_inter ? std::max(bins, MonoInterLds(a.p.num_leaves)) : bins;
-}
-// plain gain formulas (no L1 / max_delta_step / path smoothing / monotone constraints)
-static bool SimpleGains(const KArgs& a) {
-  const SplitParams& p = a.p.sp;
-  return !p.use_l1 && !p.use_max_output && !p.use_smoothing && !p.use_mc;
+  return a.p.mono_inter ? std::max(FindBinsLds(a), MonoInterLds(a.p.num_leaves)) : FindBinsLds(a);
 }
 template <bool ROOT>
 static void LaunchFind(const KArgs& a, hipStream_t s) {
   if (a.num_scan <= 0) return;  // a rank that owns no feature
   // (intermediate monotone: sides 2.. re-scan up to num_leaves re-bounded leaves)
   const int sides = ROOT ? 1 : (a.p.mono_inter ? 2 + a.p.num_leaves : 2);
-  const dim3 g(a.num_scan, sides);
+  const int ncat = a.p.vote_phase == 2 ? a.num_scan : a.p.has_cat;  // voting: every elected slot
   const size_t lds = FindLds(a);
-  const bool simple = SimpleGains(a);
-  const bool narrow = a.p.max_feature_bins <= kWave;  // (categorical scans keep kFindThreads)
-  const dim3 b(narrow ? kWave : kFindThreads), bc(kFindThreads);
-  if (a.p.has_cat) {
-    if (narrow) {
-      if (simple) hipLaunchKernelGGL((k_find<ROOT, 1, true, kWave>), g, b, lds, s, a);
-      else hipLaunchKernelGGL((k_find<ROOT, 1, false, kWave>), g, b, lds, s, a);
-    } else {
-      if (simple) hipLaunchKernelGGL((k_find<ROOT, 1, true, kFindThreads>), g, b, lds, s, a);
-      else hipLaunchKernelGGL((k_find<ROOT, 1, false, kFindThreads>), g, b, lds, s, a);
-    }
-    const int ncat = a.p.vote_phase == 2 ? a.num_scan : a.p.has_cat;  // voting: every elected slot
-    if (a.p.has_cat > 0 && a.p.wide_cat) hipLaunchKernelGGL((k_find<ROOT, 3, false, kFindThreads>), dim3(ncat, sides), bc, lds, s, a);
-    else if (a.p.has_cat > 0) hipLaunchKernelGGL((k_find<ROOT, 2, false, kFindThreads>), dim3(ncat, sides), bc, lds, s, a);
-  } else if (narrow) {
-    if (simple) hipLaunchKernelGGL((k_find<ROOT, 0, true, kWave>), g, b, lds, s, a);
-    else hipLaunchKernelGGL((k_find<ROOT, 0, false, kWave>), g, b, lds, s, a);
-  } else {
-    if (simple) hipLaunchKernelGGL((k_find<ROOT, 0, true, kFindThreads>), g, b, lds, s, a);
-    else hipLaunchKernelGGL((k_find<ROOT, 0, false, kFindThreads>), g, b, lds, s, a);
-  }
+  DispatchScans(a, [&](auto kind, auto simple, auto nt) {
+    hipLaunchKernelGGL((k_find<ROOT, kind(), simple(), nt()>), dim3(kind() >= 2 ? ncat : a.num_scan, sides),
+                       dim3(nt()), lds, s, a);
+  });
 }
 void FindRoot(const KArgs& a, hipStream_t s) { LaunchFind<true>(a, s); }
 void FindStep(const KArgs& a, hipStream_t s) { LaunchFind<false>(a, s); }

@@ -114,6 +114,36 @@ CASES = {
                               20000),
 }
 
+# Every way the split scans materialise a histogram (StageHistogram, src/device/find_stage.h), in
+# k_find (LGBM_AMD_ROUND_K=1: one split per step) and in k_round_find (=8: round growth), at small
+# shapes.  With LGBM_AMD_BLK_MIN_ROWS=256 a parent of `rows` rows -- far below split_grid x 256 --
+# is histogrammed in ceil(rows / 256) row blocks: HistBlocksFor for a step, and for a round the
+# plan's block size (RoundPlanBody, "row blocks: one size for the round"), which is
+# ceil(rows of the round / (grid - expansions)) < 256 raised to blk_min_rows, so each expansion
+# has ceil(its rows / 256) blocks as well.  A scan sums up to kDirectChunk = 16 blocks itself.
+#   stage_spread_wave:  3000 rows, at most 15 bins: the one-wave kernels.  The first split's
+#                       parent has 12 blocks, later ones 2 .. 11: partials summed by every thread
+#                       and combined in LDS ("spread") at 64 threads; leaves under 256 rows have
+#                       one block (the plain direct sum of one partial).
+#   stage_spread_chunk: 3000 rows, one 255-bin feature among 63-bin ones: the 256-thread kernels;
+#                       the 63-bin features spread (2 x 63 <= 256), the 255-bin one sums its 12 ..
+#                       2 partials per bin in chunks of independent loads.
+#   stage_reduced:      6000 rows, the same bins: the first parent has 24 blocks > 16, so the
+#                       scan reads the reduced buffer; its descendants fall back to direct sums.
+#   *_dp:               the same with gpu_use_dp: two words per bin in the partials (units == 2).
+# In all of them the larger child of every split is the parent minus the histogrammed child.
+_STAGE_BINS = {
+    "stage_spread_wave": ({"max_bin": 15}, 3000),
+    "stage_spread_chunk": ({"max_bin_by_feature": [255] + [63] * 9}, 3000),
+    "stage_reduced": ({"max_bin_by_feature": [255] + [63] * 9}, 6000),
+}
+for _name, (_extra, _rows) in _STAGE_BINS.items():
+    for _dp in (False, True):
+        for _k in ("1", "8"):
+            CASES["%s%s_k%s" % (_name, "_dp" if _dp else "", _k)] = (
+                dict(_extra, **({"gpu_use_dp": True} if _dp else {}),
+                     _env={"LGBM_AMD_BLK_MIN_ROWS": "256", "LGBM_AMD_ROUND_K": _k}), _rows)
+
 
 def _group_bins(ds):
     ng = ctypes.c_int(0)
