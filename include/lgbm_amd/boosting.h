@@ -91,6 +91,12 @@ class GBDT {
   virtual void AddValidDataset(const Dataset* valid_data, const std::vector<const Metric*>& valid_metrics);
   void Train(int snapshot_freq, const std::string& model_output_path);
   virtual bool TrainOneIter(const score_t* gradients, const score_t* hessians);
+  // one iteration from a custom objective's gradients / hessians in device memory (len =
+  // num_data * num_tree_per_iteration of dtype 0 float32 / 1 float64 / 2 float16 / 3 bfloat16,
+  // class-major and contiguous): the device learner converts them into its own arrays
+  // (DeviceTreeLearner::IngestGradients) and the iteration runs as TrainOneIter does with a
+  // custom objective's host gradients, without their upload.  Needs a device learner
+  virtual bool TrainOneIterDevice(const void* d_grad, const void* d_hess, int dtype, int64_t len);
   virtual void RollbackOneIter();
   // new leaf values for every tree from the training data's leaf matrix (row-major
   // [nrow][ncol], one column per tree: the C API's layout); the vector form wraps it
@@ -105,6 +111,15 @@ class GBDT {
   std::vector<double> GetEvalAt(int data_idx);
   virtual const double* GetTrainingScore(int64_t* out_len);
   void GetPredictAt(int data_idx, double* out, int64_t* out_len);
+  // GetPredictAt into out_len = GetNumPredictAt(data_idx) doubles of device memory (convert:
+  // through the objective's output transform where GetPredictAt applies it, else raw).  The
+  // training scores and the validation sets that live on the device are exported from HBM
+  // (src/device/custom_kernels.hip); a validation set kept on the host, or an objective whose
+  // transform has no device form, is evaluated on the host and uploaded.  Needs a device learner
+  void GetPredictAtDevice(int data_idx, bool convert, double* d_out, int64_t out_len);
+  int DeviceLearnerId() const;  // the HIP device of the device learner, or -1
+  // process-wide: scores exported by the kernel / gradients ingested (tests: the device path ran)
+  static void DeviceCustomStats(int64_t* exports, int64_t* ingests);
   int64_t GetNumPredictAt(int data_idx) const;
   int GetEvalCounts() const;
   std::vector<std::string> GetEvalNames() const;
@@ -222,6 +237,8 @@ class GBDT {
   // hook run before gradients are computed from the training score (DART drops trees here)
   virtual void PrepareScoreForGradients() {}
   virtual void Boosting();
+  // TrainOneIter; ingested: the gradients are the device learner's own arrays, already filled
+  bool TrainOneIterBody(const score_t* gradients, const score_t* hessians, bool ingested);
   virtual void Bagging(int iter);
   virtual data_size_t BaggingHelper(data_size_t start, data_size_t cnt, data_size_t* buffer);
   void ResetBaggingConfig(const Config* config, bool is_change_dataset);
@@ -327,6 +344,7 @@ class DART : public GBDT {
             const std::vector<const Metric*>& training_metrics) override;
   void ResetConfig(const Config* config) override;
   bool TrainOneIter(const score_t* gradients, const score_t* hessians) override;
+  bool TrainOneIterDevice(const void* d_grad, const void* d_hess, int dtype, int64_t len) override;
   const double* GetTrainingScore(int64_t* out_len) override;
   bool EvalAndCheckEarlyStopping() override;
 
@@ -376,6 +394,7 @@ class RF : public GBDT {
   void ResetTrainingData(const Dataset* train_data, const ObjectiveFunction* objective,
                          const std::vector<const Metric*>& training_metrics) override;
   bool TrainOneIter(const score_t* gradients, const score_t* hessians) override;
+  bool TrainOneIterDevice(const void* d_grad, const void* d_hess, int dtype, int64_t len) override;
   void RollbackOneIter() override;
   void AddValidDataset(const Dataset* valid_data, const std::vector<const Metric*>& valid_metrics) override;
 

@@ -337,6 +337,30 @@ LIGHTGBM_C_EXPORT int LGBM_AMD_DeviceBinCscStats(int64_t* csc_calls, int64_t* co
 // predictions this process has computed on the device, over all boosters (tests: whether a call
 // took the device path or the host predictor)
 LIGHTGBM_C_EXPORT int LGBM_AMD_DevicePredictCount(int64_t* out);
+// ---- custom objectives and metrics on device tensors (a booster trained with device_type=gpu)
+// the HIP device of the booster's device learner, or -1 (a CPU booster, a loaded model)
+LIGHTGBM_C_EXPORT int LGBM_AMD_BoosterDeviceId(BoosterHandle handle, int* out);
+// LGBM_BoosterGetPredict into d_out, out_len = num_data * num_class doubles of device memory on
+// that device, class-major (anything else is an error): the training scores (data_idx 0) and the
+// validation sets that live on the device are exported from HBM without a download, through the
+// objective's output transform when convert != 0 and the booster has an objective, raw otherwise.
+// The data is complete when the call returns
+LIGHTGBM_C_EXPORT int LGBM_AMD_BoosterGetPredictDevice(BoosterHandle handle, int data_idx, int convert, double* d_out,
+                                                       int64_t out_len);
+// LGBM_BoosterUpdateOneIterCustom with grad / hess in device memory: len = num_data * num_class
+// contiguous class-major values of dtype 0 float32, 1 float64, 2 float16, 3 bfloat16, converted
+// on the device as tensor.to(float32) converts.  The caller's work on them must have finished
+LIGHTGBM_C_EXPORT int LGBM_AMD_BoosterUpdateOneIterCustomDevice(BoosterHandle handle, const void* d_grad,
+                                                                const void* d_hess, int dtype, int64_t len,
+                                                                int* is_finished);
+// scores exported by the device kernel and gradients taken from device memory in this process,
+// over all boosters (tests: whether an iteration took the device path)
+LIGHTGBM_C_EXPORT int LGBM_AMD_DeviceCustomStats(int64_t* exports, int64_t* ingests);
+// the output transform of the export evaluated on the host (src/device/score_convert.h; no GPU
+// needed): kind 0 identity, 1 sigmoid(param * s), 2 sign(s) * s^2, 3 exp(s), 4 softmax over the
+// classes, 5 kind 1 per class; in / out are class-major [num_class][n] (out may be in)
+LIGHTGBM_C_EXPORT int LGBM_AMD_ConvertScores(int kind, double param, int num_class, int64_t n, const double* in,
+                                             double* out);
 // for external collective functions (LGBM_NetworkInitWithFunctions) that fail: makes the
 // collective that called them raise on this thread instead of using an unfilled buffer
 LIGHTGBM_C_EXPORT int LGBM_AMD_NetworkReportExternalError(const char* msg);

@@ -58,6 +58,27 @@ class DeviceTreeLearner {
   // the sampled rows' device gradients); returns the in-bag count
   virtual data_size_t DeviceSample(const DeviceSampleSpec& spec) = 0;
   virtual void DownloadGradients(score_t* g, score_t* h, int64_t n) = 0;
+  // custom objectives / metrics on the caller's device buffers (false: not here).  The exports
+  // copy the class-major training scores, or those of validation slot `slot`, into d_out
+  // (device, float64, same layout), through output transform convert_kind (0..5 of
+  // ObjectiveFunction::DeviceOutputKind with its param; -1: raw), and return after the copy
+  // finished.  IngestGradients converts len = num_tree_per_iteration * num_data gradients and
+  // hessians of dtype 0 float32 / 1 float64 / 2 float16 / 3 bfloat16 (device, contiguous) into
+  // device_gradients() / device_hessians(), ordered before the next Train() by the learner's
+  // stream; it leaves the learner as UploadGradients does
+  virtual bool ExportTrainScore(double* d_out, int convert_kind, double param) {
+    (void)d_out; (void)convert_kind; (void)param;
+    return false;
+  }
+  virtual bool ExportValidScore(int slot, double* d_out, int convert_kind, double param) {
+    (void)slot; (void)d_out; (void)convert_kind; (void)param;
+    return false;
+  }
+  virtual bool IngestGradients(const void* d_grad, const void* d_hess, int dtype, int64_t len) {
+    (void)d_grad; (void)d_hess; (void)dtype; (void)len;
+    return false;
+  }
+  virtual int device_id() const { return -1; }
   virtual score_t* device_gradients() = 0;
   virtual score_t* device_hessians() = 0;
   virtual void Synchronize() = 0;

@@ -811,13 +811,45 @@ class _EvalInfo:
         return self
 
 
+_ON_DEVICE_MARK = "_lgbm_amd_on_device"
+_GRAD_DTYPE_CODES = {"torch.float32": 0, "torch.float64": 1, "torch.float16": 2, "torch.bfloat16": 3}
+
+
+def on_device(fn):
+    """Mark a custom objective (``fobj``) or metric (``feval``) as written for GPU tensors; usable
+    as a decorator.  The callable is returned unchanged apart from the mark.
+
+    A marked callable receives ``preds`` as a float64 ``torch.Tensor`` on the booster's GPU
+    (``[n]``, or class-major ``[num_class, n]``; see :meth:`Booster.device_scores`) instead of a
+    NumPy array, and a marked ``fobj`` may return ``(grad, hess)`` as GPU tensors, which the
+    booster takes without a copy through the host.  The booster must be trained with
+    ``device_type='gpu'``."""
+    setattr(fn, _ON_DEVICE_MARK, True)
+    return fn
+
+
+def _is_on_device(fn):
+    return bool(getattr(fn, _ON_DEVICE_MARK, False))
+
+
+def _is_gpu_tensor(x):
+    return type(x).__module__.startswith("torch") and hasattr(x, "is_cuda") and bool(x.is_cuda)
+
+
 class _ScoreCache:
     """Raw scores of the training / validation datasets, fetched once per iteration (for
-    custom objectives and metrics)."""
+    custom objectives and metrics): NumPy buffers for plain callables, and, independent of
+    them, GPU tensors for callables marked with :func:`on_device`."""
 
     def __init__(self):
         self.buffers = []
         self.fresh = []
+        self.device = {}  # (idx, raw) -> [tensor, fresh]
+
+    def __getstate__(self):
+        state = self.__dict__.copy()
+        state["device"] = {}  # (GPU tensors stay with the live booster)
+        return state
 
     def add(self):
         self.buffers.append(None)
@@ -825,6 +857,27 @@ class _ScoreCache:
 
     def invalidate(self):
         self.fresh = [False] * len(self.buffers)
+        for entry in self.device.values():
+            entry[1] = False
+
+    def drop_device(self, idx):
+        self.device = {k: v for k, v in self.device.items() if k[0] != idx}
+
+    def get_device(self, handle, idx, n, num_class, raw, device_id):
+        import torch
+        shape = (n,) if num_class == 1 else (num_class, n)
+        entry = self.device.get((idx, raw))
+        if entry is None or tuple(entry[0].shape) != shape:
+            entry = [torch.empty(shape, dtype=torch.float64, device=torch.device("cuda", device_id)), False]
+            self.device[(idx, raw)] = entry
+        if not entry[1]:
+            t = entry[0]
+            torch.cuda.synchronize(t.device)  # (the caller's reads of the last iteration's scores)
+            with torch.cuda.device(t.device):
+                nat.call("LGBM_AMD_BoosterGetPredictDevice", handle, nat.c_int(idx), nat.c_int(0 if raw else 1),
+                         ctypes.c_void_p(t.data_ptr()), ctypes.c_int64(t.numel()))
+            entry[1] = True
+        return entry[0]
 
     def get(self, handle, idx, n):
         if self.buffers[idx] is None:
@@ -1001,7 +1054,14 @@ class Booster:
 
     # ------------------------------------------------------------------ training
     def update(self, train_set=None, fobj=None):
-        """One boosting iteration; True when training cannot continue."""
+        """One boosting iteration; True when training cannot continue.
+
+        ``fobj(preds, train_set)`` returns ``(grad, hess)``.  An ``fobj`` marked with
+        :func:`on_device` receives ``preds`` as the GPU tensor of :meth:`device_scores` (owned by
+        the booster and overwritten at the next iteration) and may return GPU tensors on the same
+        device: float16, bfloat16, float32 or float64, both of one dtype, of shape ``[len]`` or
+        ``[num_class, n]``; the booster converts them on the device.  Whatever else it returns
+        (NumPy arrays, CPU tensors) goes the way an unmarked callable's result goes."""
         stale = self.train_set_version != self.train_set.version
         if train_set is None and stale:
             train_set = self.train_set
@@ -1013,6 +1073,7 @@ class Booster:
             self.train_set = train_set
             nat.call("LGBM_BoosterResetTrainingData", self.handle, train_set.construct().handle)
             self._scores.buffers[0] = None
+            self._scores.drop_device(0)
             self.train_set_version = train_set.version
         if fobj is None:
             if self._objective_none:
@@ -1021,11 +1082,54 @@ class Booster:
             nat.call("LGBM_BoosterUpdateOneIter", self.handle, ctypes.byref(finished))
             self._scores.invalidate()
             return finished.value == 1
+        marked = _is_on_device(fobj)
+        if marked:
+            self._booster_device()  # (raises without a device learner, before anything changes)
         if not self._objective_none:
             self.reset_parameter({"objective": "none"})
             self._objective_none = True
-        grad, hess = fobj(self._dataset_scores(0), self.train_set)
+        if not marked:
+            grad, hess = fobj(self._dataset_scores(0), self.train_set)
+            return self._boost_custom(grad, hess)
+        grad, hess = fobj(self._device_dataset_scores(0), self.train_set)
+        if _is_gpu_tensor(grad) or _is_gpu_tensor(hess):
+            return self._boost_custom_device(grad, hess)
         return self._boost_custom(grad, hess)
+
+    def _booster_device(self):
+        """The GPU of the booster's device learner; an error for a booster without one."""
+        dev = self._query_int("LGBM_AMD_BoosterDeviceId") if self.handle is not None else -1
+        if dev < 0:
+            raise LightGBMError("A callable marked with on_device needs a booster trained with device_type=gpu: "
+                                "this booster keeps its scores on the host")
+        return dev
+
+    def _boost_custom_device(self, grad, hess):
+        """One iteration from GPU tensors (LGBM_AMD_BoosterUpdateOneIterCustomDevice)."""
+        import torch
+        dev = self._booster_device()
+        n, k = self.train_set.num_data(), self._num_class
+        flat = []
+        for name, t in (("gradient", grad), ("hessian", hess)):
+            if not _is_gpu_tensor(t):
+                raise ValueError("{} must be a GPU tensor when the other one is, got {}".format(name, type(t).__name__))
+            if t.device.index != dev:
+                raise ValueError("{} is on {}, the booster trains on cuda:{}".format(name, t.device, dev))
+            if str(t.dtype) not in _GRAD_DTYPE_CODES:
+                raise ValueError("{} has dtype {}: float16, bfloat16, float32 or float64 expected".format(name, t.dtype))
+            if tuple(t.shape) not in ((n * k,), (k, n)):
+                raise ValueError("{} has shape {}, expected [{}] or [{}, {}]".format(name, tuple(t.shape), n * k, k, n))
+            flat.append(t.detach().contiguous().reshape(-1))
+        if flat[0].dtype != flat[1].dtype:
+            raise ValueError("gradient ({}) and hessian ({}) must have the same dtype".format(flat[0].dtype, flat[1].dtype))
+        finished = ctypes.c_int(0)
+        torch.cuda.synchronize(flat[0].device)
+        with torch.cuda.device(flat[0].device):
+            nat.call("LGBM_AMD_BoosterUpdateOneIterCustomDevice", self.handle, ctypes.c_void_p(flat[0].data_ptr()),
+                     ctypes.c_void_p(flat[1].data_ptr()), nat.c_int(_GRAD_DTYPE_CODES[str(flat[0].dtype)]),
+                     ctypes.c_int64(flat[0].numel()), ctypes.byref(finished))
+        self._scores.invalidate()
+        return finished.value == 1
 
     def _boost_custom(self, grad, hess):
         grad = np.ascontiguousarray(inp.vector(grad, np.float32, "gradient"))
@@ -1063,6 +1167,25 @@ class Booster:
         ds = self.train_set if idx == 0 else self.valid_sets[idx - 1]
         return self._scores.get(self.handle, idx, ds.num_data() * self._num_class)
 
+    def _device_dataset_scores(self, idx, raw=False):
+        dev = self._booster_device()
+        if idx < 0 or idx >= self._num_datasets():
+            raise ValueError("Data_idx should be smaller than number of dataset")
+        ds = self.train_set if idx == 0 else self.valid_sets[idx - 1]
+        return self._scores.get_device(self.handle, idx, ds.num_data(), self._num_class, bool(raw), dev)
+
+    def device_scores(self, data_idx=0, raw=False):
+        """The booster's current scores of the training data (``data_idx=0``) or of validation set
+        ``data_idx - 1`` as a float64 ``torch.Tensor`` on the booster's GPU, without a copy through
+        the host: shape ``[n]``, or ``[num_class, n]`` with several trees per iteration (flattened,
+        the class-major vector a NumPy ``fobj`` / ``feval`` receives).  As for those, the values
+        went through the objective's output transform unless ``raw`` or the objective is custom.
+
+        This is the tensor a callable marked with :func:`on_device` receives.  It is owned by the
+        booster and overwritten in place at the next request after the model changed (``update``,
+        ``rollback_one_iter``): clone it to keep an iteration's values.  Needs ``device_type='gpu'``."""
+        return self._device_dataset_scores(data_idx, raw)
+
     def _evaluate(self, name, idx, feval):
         if idx >= self._num_datasets():
             raise ValueError("Data_idx should be smaller than number of dataset")
@@ -1082,7 +1205,8 @@ class Booster:
             for fn in fns:
                 if fn is None:
                     continue
-                res = fn(self._dataset_scores(idx), data)
+                # (a callable marked with on_device takes the scores as a GPU tensor)
+                res = fn(self._device_dataset_scores(idx) if _is_on_device(fn) else self._dataset_scores(idx), data)
                 for metric, val, hb in (res if isinstance(res, list) else [res]):
                     out.append((name, metric, val, hb))
         return out

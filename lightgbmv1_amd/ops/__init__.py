@@ -30,6 +30,11 @@ the kernels can be checked one by one against plain PyTorch references
 * :func:`csc_group_bins` -- the same matrix from the columns of a CSC matrix, by the kernels that
   bin a scipy CSC matrix (src/device/csc_bin_kernels.hip); :func:`csc_bin_launch_info` gives
   their launch shape
+* :func:`convert_scores` / :func:`cast_gradients` -- the two kernels behind custom objectives and
+  metrics marked with ``lightgbmv1_amd.on_device`` (src/device/custom_kernels.hip): an
+  objective's output transform of raw scores (src/device/score_convert.h; reference
+  ObjectiveFunction::ConvertOutput) and float16 / bfloat16 / float32 / float64 gradients as the
+  learner's float32; :func:`custom_launch_info` gives their launch shape
 
 There is no host fallback: the ops need a GPU and the in-tree library.
 """
@@ -41,7 +46,8 @@ from .._native import LightGBMError, call as _native_call, params_str as param_d
 from ..basic import _load_lib
 
 __all__ = ["gradients", "metric", "sample_rows", "forest_predict", "leaf_sums", "add_leaf_values",
-           "refit_launch_info", "csc_launch_info", "csr_group_bins", "csr_bin_launch_info"]
+           "refit_launch_info", "csc_launch_info", "csr_group_bins", "csr_bin_launch_info",
+           "convert_scores", "cast_gradients", "custom_launch_info"]
 
 
 def _torch():
@@ -399,3 +405,59 @@ def add_leaf_values(score, leaf, values):
                                           _dev_ptr(values, torch.float64, "values"), ctypes.c_int64(n),
                                           ctypes.c_int32(values.numel())))
     return score
+
+
+_GRAD_DTYPES = {"torch.float32": 0, "torch.float64": 1, "torch.float16": 2, "torch.bfloat16": 3}
+
+
+def custom_launch_info():
+    """The launch shape of the kernels behind :func:`convert_scores` and :func:`cast_gradients`
+    (src/device/custom_kernels.hip): ``block`` (threads of a workgroup), ``per_thread`` (elements a
+    thread has in flight per loop trip, ``grid * block`` apart) and ``max_grid`` (the most
+    workgroups of a launch: more than ``max_grid * block * per_thread`` elements make a thread loop)."""
+    out = (ctypes.c_int64 * 3)()
+    _check(_lib().LGBMAMD_OpCustomLaunchInfo(out))
+    return {"block": out[0], "per_thread": out[1], "max_grid": out[2]}
+
+
+def convert_scores(params, score):
+    """The output transform of ``params["objective"]`` (sigmoid for ``binary``, softmax over the
+    classes for ``multiclass``, ...; no objective or ``"none"``: a copy) of raw scores, a float64 GPU
+    tensor ``[n]`` or class-major ``[num_class, n]``, by the kernel that hands a booster's scores
+    to a metric marked with ``lightgbmv1_amd.on_device`` (``k_export_scores``).  Returns a new
+    tensor of the same shape; ``LGBM_AMD_ConvertScores`` is the same rule on the host."""
+    torch = _torch()
+    ptr = _dev_ptr(score, torch.float64, "score")
+    if score.dim() not in (1, 2):
+        raise LightGBMError("score must have shape [n] or [num_class, n]")
+    num_class = 1 if score.dim() == 1 else score.shape[0]
+    n = score.shape[-1]
+    out = torch.empty_like(score)
+    torch.cuda.synchronize(score.device)
+    with torch.cuda.device(score.device):
+        _check(_lib().LGBMAMD_OpConvertScores(ctypes.c_char_p(_params(params)), ptr, ctypes.c_int32(num_class),
+                                              ctypes.c_int64(n), _dev_ptr(out, torch.float64, "out"), None, None))
+    return out
+
+
+def cast_gradients(grad, hess):
+    """``grad`` and ``hess`` (contiguous GPU tensors of one shape and one dtype out of float16,
+    bfloat16, float32 and float64) as float32 tensors, by the kernel that takes the tensors a
+    custom objective marked with ``lightgbmv1_amd.on_device`` returns (``k_ingest_gradients``):
+    the values of ``tensor.to(torch.float32)``."""
+    torch = _torch()
+    if not isinstance(grad, torch.Tensor) or not isinstance(hess, torch.Tensor):
+        raise LightGBMError("grad and hess must be torch tensors on the GPU")
+    if str(grad.dtype) not in _GRAD_DTYPES:
+        raise LightGBMError("grad has dtype %s: float16, bfloat16, float32 or float64 expected" % grad.dtype)
+    if hess.dtype != grad.dtype or hess.shape != grad.shape or hess.device != grad.device:
+        raise LightGBMError("grad and hess must have the same dtype, shape and device")
+    gp, hp = _dev_ptr(grad, grad.dtype, "grad"), _dev_ptr(hess, hess.dtype, "hess")
+    out_g = torch.empty(grad.shape, dtype=torch.float32, device=grad.device)
+    out_h = torch.empty_like(out_g)
+    torch.cuda.synchronize(grad.device)
+    with torch.cuda.device(grad.device):
+        _check(_lib().LGBMAMD_OpCastGradients(gp, hp, ctypes.c_int32(_GRAD_DTYPES[str(grad.dtype)]),
+                                              ctypes.c_int64(grad.numel()), _dev_ptr(out_g, torch.float32, "out"),
+                                              _dev_ptr(out_h, torch.float32, "out")))
+    return out_g, out_h

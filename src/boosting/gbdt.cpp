@@ -527,6 +527,10 @@ bool GBDT::SpeculationSafe(bool own_gradients) const {
 }
 
 bool GBDT::TrainOneIter(const score_t* gradients, const score_t* hessians) {
+  return TrainOneIterBody(gradients, hessians, false);
+}
+
+bool GBDT::TrainOneIterBody(const score_t* gradients, const score_t* hessians, bool ingested) {
   common::ScopedTimer timer("GBDT::TrainOneIter");
   if (!iter_log_checked_) {
     iter_log_checked_ = true;
@@ -556,7 +560,7 @@ bool GBDT::TrainOneIter(const score_t* gradients, const score_t* hessians) {
       grad = gradients_.data();
       hess = hessians_.data();
     }
-  } else if (device_learner_ != nullptr) {
+  } else if (device_learner_ != nullptr && !ingested) {
     const int64_t total = static_cast<int64_t>(num_data_) * num_tree_per_iteration_;
     device_learner_->UploadGradients(gradients, hessians, total);
     grad = device_learner_->device_gradients();

@@ -43,6 +43,17 @@ bool DART::TrainOneIter(const score_t* g, const score_t* h) {
   return false;
 }
 
+bool DART::TrainOneIterDevice(const void* d_grad, const void* d_hess, int dtype, int64_t len) {
+  is_update_score_cur_iter_ = false;
+  if (GBDT::TrainOneIterDevice(d_grad, d_hess, dtype, len)) return true;
+  Normalize();
+  if (!config_->uniform_drop) {
+    tree_weight_.push_back(shrinkage_rate_);
+    sum_weight_ += shrinkage_rate_;
+  }
+  return false;
+}
+
 void DART::PrepareScoreForGradients() {
   if (!is_update_score_cur_iter_) {
     DroppingTrees();
@@ -320,6 +331,11 @@ bool RF::TrainOneIter(const score_t* g, const score_t* h) {
   }
   ++iter_;
   return false;
+}
+
+bool RF::TrainOneIterDevice(const void*, const void*, int, int64_t) {
+  Log::Fatal("RF mode do not support custom objective function, please use built-in objectives.");
+  return true;
 }
 
 void RF::RollbackOneIter() {

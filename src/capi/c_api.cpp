@@ -39,6 +39,7 @@
 #include "../device/csc_bins.h"
 #include "../device/kernels.h"
 #include "../device/refit_quant.h"
+#include "../device/score_convert.h"
 #include "../treelearner/growth_limits.h"
 
 using namespace lgbm_amd;
@@ -1911,6 +1912,42 @@ int LGBM_AMD_DeviceBinCscStats(int64_t* csc_calls, int64_t* column_samples) {
 int LGBM_AMD_DevicePredictCount(int64_t* out) {
   API_BEGIN();
   *out = GBDT::DevicePredictions();
+  API_END();
+}
+
+int LGBM_AMD_BoosterDeviceId(BoosterHandle handle, int* out) {
+  API_BEGIN();
+  const auto booster_lock = ReadLock(handle);
+  *out = static_cast<Booster*>(handle)->boosting()->DeviceLearnerId();
+  API_END();
+}
+
+int LGBM_AMD_BoosterGetPredictDevice(BoosterHandle handle, int data_idx, int convert, double* d_out, int64_t out_len) {
+  API_BEGIN();
+  const auto booster_lock = WriteLock(handle);  // (the export launches on the learner's stream)
+  static_cast<Booster*>(handle)->boosting()->GetPredictAtDevice(data_idx, convert != 0, d_out, out_len);
+  API_END();
+}
+
+int LGBM_AMD_BoosterUpdateOneIterCustomDevice(BoosterHandle handle, const void* d_grad, const void* d_hess, int dtype,
+                                              int64_t len, int* is_finished) {
+  API_BEGIN();
+  const auto booster_lock = WriteLock(handle);
+  *is_finished = static_cast<Booster*>(handle)->boosting()->TrainOneIterDevice(d_grad, d_hess, dtype, len) ? 1 : 0;
+  API_END();
+}
+
+int LGBM_AMD_DeviceCustomStats(int64_t* exports, int64_t* ingests) {
+  API_BEGIN();
+  GBDT::DeviceCustomStats(exports, ingests);
+  API_END();
+}
+
+int LGBM_AMD_ConvertScores(int kind, double param, int num_class, int64_t n, const double* in, double* out) {
+  API_BEGIN();
+  if (kind < 0 || kind >= dev::kConvertKinds) Log::Fatal("ConvertScores: kind %d is not one of 0..5", kind);
+  if (num_class < 1 || n < 0) Log::Fatal("ConvertScores: need num_class >= 1 and n >= 0");
+  dev::EvalConvertScores(kind, param, num_class, n, in, out);
   API_END();
 }
 

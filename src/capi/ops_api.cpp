@@ -8,8 +8,10 @@
 // tests/test_rank_ops.py); a booster's forest prediction (scores, leaf indices, SHAP
 // contributions) on a matrix that already is on the device; and the two per-tree passes of a
 // device refit (src/device/refit_kernels.hip: per-leaf sums, score update; tests/test_device_refit.py);
-// and the CSR / CSC binning kernels under a dataset's bin mappers (src/device/csr_bin_kernels.hip,
-// src/device/csc_bin_kernels.hip).
+// the CSR / CSC binning kernels under a dataset's bin mappers (src/device/csr_bin_kernels.hip,
+// src/device/csc_bin_kernels.hip); and the two kernels behind custom objectives and metrics on
+// device tensors (src/device/custom_kernels.hip: score export with an objective's output
+// transform, gradient ingest; tests/test_device_custom_objective.py).
 //
 // Objectives and metrics are created from a parameter string exactly as training creates
 // them (reference objective_function.cpp:16-56, metric.cpp:16-63), so the kernels see the
@@ -515,5 +517,79 @@ LIGHTGBM_C_EXPORT int LGBMAMD_OpSampleRows(int64_t n, int32_t seed, int32_t goss
     dev::SampleRows(s, nullptr);
     OPCHECK(hipGetLastError());
     OPCHECK(hipMemcpy(out_count, s.bag_count, sizeof(int32_t), hipMemcpyDeviceToHost));
+  });
+}
+
+// the output transform of objective `params` on raw scores, by the kernel that exports a
+// booster's scores to a marked custom metric (src/device/custom_kernels.hip k_export_scores):
+// d_score / d_out (device, float64) are class-major [num_class][n]; out_kind / out_param receive
+// the transform (ObjectiveFunction::DeviceOutputKind; LGBM_AMD_ConvertScores evaluates it on the
+// host).  No objective ("none"): a raw copy, kind 0
+LIGHTGBM_C_EXPORT int LGBMAMD_OpConvertScores(const char* params, const double* d_score, int32_t num_class, int64_t n,
+                                              double* d_out, int32_t* out_kind, double* out_param) {
+  return Guard([&] {
+    Config c = ParseConfig(params);
+    std::unique_ptr<ObjectiveFunction> obj;
+    // ("none" reaches here under its canonical name "custom")
+    if (!c.objective.empty() && c.objective != "none" && c.objective != "custom") {
+      obj.reset(ObjectiveFunction::CreateObjectiveFunction(c.objective, c));
+      if (!obj) Log::Fatal("op convert_scores: no objective '%s'", c.objective.c_str());
+    }
+    double param = 0.0;
+    const int kind = obj ? obj->DeviceOutputKind(&param) : 0;
+    if (kind < 0 || kind > 5) {
+      Log::Fatal("op convert_scores: the output transform of '%s' has no device kernel", c.objective.c_str());
+    }
+    if (num_class < 1 || n < 0) Log::Fatal("op convert_scores: need num_class >= 1 and n >= 0");
+    if (obj && obj->NumModelPerIteration() != num_class) {
+      Log::Fatal("op convert_scores: '%s' has %d scores per row, the tensor has %d", c.objective.c_str(),
+                 obj->NumModelPerIteration(), num_class);
+    }
+    dev::ExportArgs e{};
+    tuning::PoisonArgs(&e);  // (every field set below)
+    e.score = d_score;
+    e.out = d_out;
+    e.n = n;
+    e.num_class = num_class;
+    e.convert = obj ? 1 : 0;
+    e.kind = kind;
+    e.param = param;
+    dev::ExportScores(e, nullptr);
+    OPCHECK(hipGetLastError());
+    OPCHECK(hipDeviceSynchronize());
+    if (out_kind != nullptr) *out_kind = kind;
+    if (out_param != nullptr) *out_param = param;
+  });
+}
+
+// len gradients and hessians (device, contiguous; dtype 0 float32, 1 float64, 2 float16,
+// 3 bfloat16) into float32 d_out_grad / d_out_hess by the kernel that takes a marked custom
+// objective's tensors (k_ingest_gradients)
+LIGHTGBM_C_EXPORT int LGBMAMD_OpCastGradients(const void* d_grad, const void* d_hess, int32_t dtype, int64_t len,
+                                              float* d_out_grad, float* d_out_hess) {
+  return Guard([&] {
+    if (len < 0) Log::Fatal("op cast_gradients: need len >= 0");
+    dev::IngestArgs g{};
+    tuning::PoisonArgs(&g);  // (every field set below)
+    g.grad = d_grad;
+    g.hess = d_hess;
+    g.out_grad = d_out_grad;
+    g.out_hess = d_out_hess;
+    g.len = len;
+    g.dtype = dtype;
+    if (!dev::IngestGradients(g, nullptr)) Log::Fatal("op cast_gradients: dtype %d is not one of 0..3", dtype);
+    OPCHECK(hipGetLastError());
+    OPCHECK(hipDeviceSynchronize());
+  });
+}
+
+// the launch shape of the two kernels (tests size their inputs from it): out[0] threads per
+// workgroup, out[1] elements per thread and loop trip (a thread's elements are grid * out[0]
+// apart), out[2] the most workgroups of a launch
+LIGHTGBM_C_EXPORT int LGBMAMD_OpCustomLaunchInfo(int64_t* out) {
+  return Guard([&] {
+    out[0] = dev::kCustomThreads;
+    out[1] = dev::kCustomPerThread;
+    out[2] = dev::CustomGridCap();
   });
 }

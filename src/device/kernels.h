@@ -767,6 +767,34 @@ void RefitAddLeafValues(const RefitAddArgs& a, hipStream_t s);
 // workgroups of the leaf-sum pass over n rows (each thread strides by grid * kRefitThreads)
 int RefitSumGrid(int64_t n);
 
+// ---- custom objectives / metrics on the caller's device buffers (src/device/custom_kernels.hip)
+constexpr int kCustomThreads = 256;
+constexpr int kCustomPerThread = 4;  // elements in flight per thread and loop trip (grid * kCustomThreads apart)
+// class-major float64 scores ([num_class][n]: the training scores, a validation slot) into a
+// buffer of the same layout; convert != 0: through output transform `kind` (score_convert.h)
+struct ExportArgs {
+  const double* score{};
+  double* out{};
+  int64_t n{};
+  int32_t num_class{};
+  int32_t convert{};
+  int32_t kind{};   // 0..5 (ObjectiveFunction::DeviceOutputKind), read when convert != 0
+  double param{};   // the sigmoid parameter of kinds 1 and 5
+};
+void ExportScores(const ExportArgs& a, hipStream_t s);
+// len gradients and hessians of dtype kGrad* (contiguous) as floats into out_grad / out_hess
+constexpr int kGradF32 = 0, kGradF64 = 1, kGradF16 = 2, kGradBF16 = 3;
+struct IngestArgs {
+  const void* grad{};
+  const void* hess{};
+  float* out_grad{};
+  float* out_hess{};
+  int64_t len{};
+  int32_t dtype{};
+};
+bool IngestGradients(const IngestArgs& a, hipStream_t s);  // false: no such dtype (nothing launched)
+int CustomGridCap();  // the most workgroups of either launch
+
 int GradientBlocks(int64_t n);
 // absmax = (max |g|, max h, rows_cap, 0) (and root = (sum g, sum h, n) if root_parts) from
 // per-workgroup partials

@@ -1,5 +1,6 @@
 // MI355X tree learner: validation sets, device-resident training scores, gradients and
 // row sampling.
+#include "../device/score_convert.h"
 #include "gpu_learner_internal.h"
 #include "lgbm_amd/tuning.h"
 
@@ -615,6 +616,63 @@ void GPUTreeLearner::UploadGradients(const score_t* g, const score_t* h, int64_t
   HIPCHECK(hipMemcpyAsync(d_grad_, g, sizeof(float) * n, hipMemcpyHostToDevice, stream_));
   HIPCHECK(hipMemcpyAsync(d_hess_, h, sizeof(float) * n, hipMemcpyHostToDevice, stream_));
   HIPCHECK(hipStreamSynchronize(stream_));
+}
+
+// ---------------------------------------------------------------- custom objectives / metrics on device tensors
+// scores [ntpi][n] out to the caller's buffer (src/device/custom_kernels.hip); the caller reads
+// it on a stream of its own, so the copy is finished on return
+bool GPUTreeLearner::ExportScores(const double* score, int64_t n, int ntpi, double* d_out, int convert_kind,
+                                  double param) {
+  if (score == nullptr || d_out == nullptr || convert_kind >= dev::kConvertKinds) return false;
+  HIPCHECK(hipSetDevice(device_id_));
+  dev::ExportArgs e{};
+  tuning::PoisonArgs(&e);  // (every field set below)
+  e.score = score;
+  e.out = d_out;
+  e.n = n;
+  e.num_class = ntpi;
+  e.convert = convert_kind >= 0 ? 1 : 0;
+  e.kind = convert_kind >= 0 ? convert_kind : 0;
+  e.param = param;
+  dev::ExportScores(e, stream_);
+  HIPCHECK(hipGetLastError());
+  HIPCHECK(hipStreamSynchronize(stream_));
+  return true;
+}
+
+bool GPUTreeLearner::ExportTrainScore(double* d_out, int convert_kind, double param) {
+  return ExportScores(d_score_, num_data_, num_tree_per_iteration_, d_out, convert_kind, param);
+}
+
+bool GPUTreeLearner::ExportValidScore(int slot, double* d_out, int convert_kind, double param) {
+  if (slot < 0 || slot >= static_cast<int>(valid_.size()) || slot == train_eval_slot_) return false;
+  const ValidSet& vs = valid_[slot];
+  return ExportScores(vs.score, vs.num_data, vs.ntpi, d_out, convert_kind, param);
+}
+
+// the caller's gradients into d_grad_ / d_hess_: UploadGradients without the host (the stream
+// orders the conversion before the tree's kernels; the caller synchronised its own stream)
+bool GPUTreeLearner::IngestGradients(const void* d_grad, const void* d_hess, int dtype, int64_t len) {
+  if (d_grad_ == nullptr || d_grad == nullptr || d_hess == nullptr ||
+      len != static_cast<int64_t>(num_data_) * num_tree_per_iteration_) {
+    return false;
+  }
+  HIPCHECK(hipSetDevice(device_id_));
+  dev::IngestArgs g{};
+  tuning::PoisonArgs(&g);  // (every field set below)
+  g.grad = d_grad;
+  g.hess = d_hess;
+  g.out_grad = d_grad_;
+  g.out_hess = d_hess_;
+  g.len = len;
+  g.dtype = dtype;
+  if (!dev::IngestGradients(g, stream_)) return false;
+  HIPCHECK(hipGetLastError());  // (a failed launch would leave last iteration's gradients)
+  gh_fresh_ = false;
+  split_stale_ = false;
+  last_grad_fusable_ = false;
+  grad_prefetched_ = false;
+  return true;
 }
 
 void GPUTreeLearner::DownloadGradients(score_t* g, score_t* h, int64_t n) {

@@ -76,6 +76,10 @@ class GPUTreeLearner : public SerialTreeLearner, public DeviceTreeLearner {
   void UploadGradients(const score_t* g, const score_t* h, int64_t n) override;
   data_size_t DeviceSample(const DeviceSampleSpec& spec) override;
   void DownloadGradients(score_t* g, score_t* h, int64_t n) override;
+  bool ExportTrainScore(double* d_out, int convert_kind, double param) override;
+  bool ExportValidScore(int slot, double* d_out, int convert_kind, double param) override;
+  bool IngestGradients(const void* d_grad, const void* d_hess, int dtype, int64_t len) override;
+  int device_id() const override { return device_id_; }
   score_t* device_gradients() override { return d_grad_; }
   score_t* device_hessians() override { return d_hess_; }
   void Synchronize() override;
@@ -183,6 +187,7 @@ class GPUTreeLearner : public SerialTreeLearner, public DeviceTreeLearner {
   // assumed (the walk's gradients, nothing reset); otherwise the launched tree is drained and
   // the tree grown again with the same feature sample.
   bool SpeculationEligible() const;
+  bool ExportScores(const double* score, int64_t n, int ntpi, double* d_out, int convert_kind, double param);
   void LaunchSpeculative();
   void DropSpeculation();  // drain a launched next tree, restore the column sampler
   bool spec_allowed_ = false;
