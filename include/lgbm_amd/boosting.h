@@ -131,8 +131,10 @@ class GBDT {
   // predictions of a dense float32 / float64 matrix on the MI355X: normal / raw scores and leaf
   // indices as the host predictor gives them, contributions from per-leaf path tables (equal to
   // the host's recursion up to rounding).  Rows pass through the device in chunks that fit its
-  // free memory.  false if not applicable: no device, too many classes, or for contributions a
-  // path longer than the kernel holds or a node without data_count (the host then predicts)
+  // free memory (src/boosting/predict_chunks.h is the rule, for the CSR and CSC entries below
+  // too).  false if not applicable: no device, too many classes, not even one tile of rows fits
+  // the free memory, or for contributions a path longer than the kernel holds or a node without
+  // data_count (the host then predicts)
   bool PredictDenseOnDevice(const void* data, bool is_double, int64_t nrow, int ncol, bool row_major,
                             int start_iteration, int num_iteration, DevicePredictKind kind, double* out);
   // the same kernels on a row-major matrix in device memory, into out_len doubles of device
@@ -143,7 +145,7 @@ class GBDT {
   // 1 entries): each chunk of rows is scattered on the device into a compact matrix of the
   // features the window's trees split on, which the same kernels walk.  Absent entries are 0,
   // columns the model does not have are ignored, the last stored entry of a column wins.  false
-  // as for the dense matrix, or when not even one tile of rows fits the free memory
+  // as for the dense matrix, or when indptr does not ascend within nelem
   bool PredictCSROnDevice(const void* indptr, bool indptr_is_64, const int32_t* indices, const void* data,
                           bool is_double, int64_t nindptr, int64_t nelem, int start_iteration, int num_iteration,
                           DevicePredictKind kind, double* out);
@@ -164,8 +166,8 @@ class GBDT {
   // the window's trees split on go to the device, where they stay for the call, and each chunk of
   // rows is scattered from them into the compact matrix.  Absent entries are 0, columns the model
   // does not have are ignored, an entry whose row is outside the matrix is dropped, and of several
-  // stored entries on one cell the last stored one wins.  false as for the CSR matrix, or when the
-  // pointer does not ascend within nelem or the entries do not fit the free memory
+  // stored entries on one cell the last stored one wins.  false as for the CSR matrix (the resident
+  // entries count against the free memory)
   bool PredictCSCOnDevice(const void* col_ptr, bool col_ptr_is_64, const int32_t* indices, const void* data,
                           bool is_double, int64_t ncol_ptr, int64_t nelem, int64_t num_row, int start_iteration,
                           int num_iteration, DevicePredictKind kind, double* out);
@@ -299,6 +301,17 @@ class GBDT {
   int start_iteration_for_pred_ = 0;
   // InitPredict, then the trees of the prediction window in model order
   std::vector<const Tree*> PredictWindowTrees(int start_iteration, int num_iteration);
+  // what the three Predict*OnDevice entries share (src/boosting/device_predict.cpp, where the row
+  // sources of the input layouts are): device probe, forest upload, the chunk plan, the loop over
+  // the chunks, the output transform
+  template <typename Source>
+  bool PredictChunksOnDevice(Source* src, int64_t nrow, int start_iteration, int num_iteration,
+                             DevicePredictKind kind, double* out);
+  // ... and the three Predict*DeviceBuffers entries: the window's forest on the null stream, after
+  // the checks of kind, class count and out_len
+  template <typename Forest>
+  void UploadForDeviceBuffers(Forest* forest, DevicePredictKind kind, bool slots, int64_t nrow, int64_t out_len,
+                              int start_iteration, int num_iteration);
   int num_init_iteration_ = 0;
   std::vector<std::string> feature_names_;
   std::vector<std::string> feature_infos_;

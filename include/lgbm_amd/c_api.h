@@ -287,6 +287,14 @@ LIGHTGBM_C_EXPORT int LGBM_AMD_CscToSlots(BoosterHandle handle, const void* col_
 // boundaries): out[0] the stored entries of a segment, the share of a column that one wave takes,
 // out[1] the threads of a workgroup, out[2] the entries of a batch of the single-wave path
 LIGHTGBM_C_EXPORT int LGBM_AMD_CscLaunchInfo(int64_t* out);
+// the rule that sizes the chunks of rows of a device prediction (src/boosting/predict_chunks.h),
+// evaluated on the host (no GPU needed): nrow rows within `budget` bytes, of which `fixed` are
+// held for the whole call, per_row for every row of a chunk and per_entry for every stored entry
+// of the fullest chunk under ptr (nrow + 1 ascending entries; null: chunks stage no entries);
+// forced > 0 sets the rows of a chunk as the test knob does.  out[0] the rows of a chunk, out[1]
+// the stored entries of its fullest chunk, out[2] whether it fits (else the host predicts)
+LIGHTGBM_C_EXPORT int LGBM_AMD_PredictChunkPlan(int64_t nrow, int64_t budget, int64_t fixed, int64_t per_row,
+                                                int64_t per_entry, int64_t forced, const int64_t* ptr, int64_t* out);
 // the per-leaf sums of a device refit, evaluated on the host with the kernel's fixed-point rule
 // (src/device/refit_quant.h; no GPU needed): leaf[n] in [0, num_leaves) (anything else is an
 // error), grad / hess[n]; out_sums[2 * num_leaves] receives sum g then sum h per leaf

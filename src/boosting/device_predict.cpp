@@ -4,8 +4,11 @@
 // thread, with the host predictor's semantics (reference GBDT::PredictRaw / Predict,
 // src/boosting/gbdt_prediction.cpp:13-64); output transforms stay on the host.  Leaf indices
 // come from the same walk and SHAP contributions from the per-leaf path tables of shap_paths.h
-// (src/device/shap_kernels.hip).  Rows go through the device in chunks sized from the free
-// memory, so that a contribution matrix larger than HBM still predicts.
+// (src/device/shap_kernels.hip).  Rows go through the device in chunks, so that a contribution
+// matrix larger than HBM still predicts: one driver (GBDT::PredictChunksOnDevice) stages, runs and
+// copies back chunk after chunk for every input layout, and one rule (predict_chunks.h) sizes
+// the chunks so that input, output and the accumulator tiles stay within four fifths of the
+// free memory.
 //
 // CSR matrices (LGBM_BoosterPredictForCSR) take the same path: each chunk's rows are scattered on
 // the device into a compact matrix with one column per feature the window's trees split on
@@ -27,6 +30,7 @@
 #include "../device/csc_slots.h"
 #include "../device/csr_slots.h"
 #include "../device/kernels.h"
+#include "predict_chunks.h"
 #include "shap_paths.h"
 #include "lgbm_amd/boosting.h"
 #include "lgbm_amd/log.h"
@@ -176,117 +180,6 @@ class DeviceForest {
   size_t phi_bytes_ = 0;
 };
 
-}  // namespace
-
-std::vector<const Tree*> GBDT::PredictWindowTrees(int start_iteration, int num_iteration) {
-  InitPredict(start_iteration, num_iteration, false);
-  const int t0 = start_iteration_for_pred_ * num_tree_per_iteration_;
-  const int nt = num_iteration_for_pred_ * num_tree_per_iteration_;
-  std::vector<const Tree*> trees(nt);
-  for (int i = 0; i < nt; ++i) trees[i] = models_[t0 + i].get();
-  return trees;
-}
-
-bool GBDT::PredictDenseOnDevice(const void* data, bool is_double, int64_t nrow, int ncol, bool row_major,
-                                int start_iteration, int num_iteration, DevicePredictKind kind, double* out) {
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return false;
-  if (num_tree_per_iteration_ > dev::kMaxPredClasses || nrow <= 0) return false;
-  // (a matrix narrower than the model, let through by predict_disable_shape_check: the kernels index
-  // a row by the model's features, and the host predictor reads the absent columns as 0)
-  if (ncol <= max_feature_idx_) return false;
-  const int ntpi = num_tree_per_iteration_;
-  // (the forest is rebuilt per call: trees may have been edited in place)
-  const std::vector<const Tree*> trees = PredictWindowTrees(start_iteration, num_iteration);
-  hipStream_t s;
-  HIPCHECK(hipStreamCreateWithFlags(&s, hipStreamNonBlocking));
-  bool ran = false;
-  {
-    DeviceForest forest;
-    if (forest.Upload(trees, ntpi, max_feature_idx_ + 1, kind, s)) {
-      const size_t elem = is_double ? 8 : 4;
-      const int64_t per_out = forest.OutPerRow();
-      // rows per chunk: input, output and the accumulator tiles within most of the free memory
-      size_t free_b = 0, total_b = 0;
-      HIPCHECK(hipMemGetInfo(&free_b, &total_b));
-      const size_t per_row = static_cast<size_t>(ncol) * elem + static_cast<size_t>(per_out) * sizeof(double);
-      const size_t budget = free_b - free_b / 5;
-      const size_t fixed = forest.ScratchBytes(nrow);
-      int64_t chunk = budget > fixed ? static_cast<int64_t>((budget - fixed) / per_row) : 0;
-      chunk = std::max<int64_t>(dev::kShapLanes, chunk / dev::kShapLanes * dev::kShapLanes);
-      const int forced = tuning::Int(tuning::Knob::PredictChunkRows, 0);
-      if (forced > 0) chunk = forced;
-      chunk = std::min(chunk, nrow);
-      DeviceBuffers b;
-      void* d_data = b.Alloc(static_cast<size_t>(chunk) * ncol * elem);
-      double* d_out = static_cast<double*>(b.Alloc(static_cast<size_t>(chunk) * per_out * sizeof(double)));
-      const bool convert = kind == DevicePredictKind::Normal;
-      std::vector<double> raw_out(convert ? static_cast<size_t>(nrow) * per_out : 0);
-      double* host_out = convert ? raw_out.data() : out;
-      for (int64_t r0 = 0; r0 < nrow; r0 += chunk) {
-        const int64_t rows = std::min(chunk, nrow - r0);
-        const char* src = static_cast<const char*>(data);
-        if (row_major) {
-          HIPCHECK(hipMemcpyAsync(d_data, src + static_cast<size_t>(r0) * ncol * elem,
-                                  static_cast<size_t>(rows) * ncol * elem, hipMemcpyHostToDevice, s));
-        } else if (rows == nrow) {
-          HIPCHECK(hipMemcpyAsync(d_data, src, static_cast<size_t>(rows) * ncol * elem, hipMemcpyHostToDevice, s));
-        } else {  // the chunk's rows of every column, compacted to a column stride of `rows`
-          HIPCHECK(hipMemcpy2DAsync(d_data, static_cast<size_t>(rows) * elem, src + static_cast<size_t>(r0) * elem,
-                                    static_cast<size_t>(nrow) * elem, static_cast<size_t>(rows) * elem, ncol,
-                                    hipMemcpyHostToDevice, s));
-        }
-        forest.Run(d_data, is_double, row_major, rows, ncol, d_out, s);
-        HIPCHECK(hipMemcpyAsync(host_out + r0 * per_out, d_out, static_cast<size_t>(rows) * per_out * sizeof(double),
-                                hipMemcpyDeviceToHost, s));
-        HIPCHECK(hipStreamSynchronize(s));
-      }
-      ran = true;
-      ++g_device_predictions;
-      if (convert) {
-#pragma omp parallel for schedule(static)
-        for (int64_t r = 0; r < nrow; ++r) {
-          double* o = out + r * ntpi;
-          std::memcpy(o, raw_out.data() + r * ntpi, sizeof(double) * ntpi);
-          if (average_output_) {
-            for (int k = 0; k < ntpi; ++k) o[k] /= num_iteration_for_pred_;
-          }
-          if (objective_ != nullptr) objective_->ConvertOutput(o, o);
-        }
-      }
-    }
-  }
-  HIPCHECK(hipStreamDestroy(s));
-  return ran;
-}
-
-void GBDT::PredictDeviceBuffers(const void* d_data, bool is_double, int64_t nrow, int ncol, int start_iteration,
-                                int num_iteration, DevicePredictKind kind, double* d_out, int64_t out_len) {
-  if (kind == DevicePredictKind::Normal) Log::Fatal("device buffers are predicted as raw scores, leaf indices or contributions");
-  if (num_tree_per_iteration_ > dev::kMaxPredClasses) {
-    Log::Fatal("forest prediction on the device handles at most %d trees per iteration", dev::kMaxPredClasses);
-  }
-  if (ncol != max_feature_idx_ + 1) {
-    Log::Fatal("The number of features in data (%d) is not the same as it was in training data (%d).", ncol,
-               max_feature_idx_ + 1);
-  }
-  const std::vector<const Tree*> trees = PredictWindowTrees(start_iteration, num_iteration);
-  DeviceForest forest;
-  if (!forest.Upload(trees, num_tree_per_iteration_, max_feature_idx_ + 1, kind, nullptr)) {
-    Log::Fatal("contributions on the device need paths of at most %d distinct features and data counts on every node",
-               dev::kShapMaxPathLen - 1);
-  }
-  if (out_len != nrow * forest.OutPerRow()) {
-    Log::Fatal("output holds %lld doubles, the prediction has %lld", static_cast<long long>(out_len),
-               static_cast<long long>(nrow * forest.OutPerRow()));
-  }
-  if (nrow > 0) forest.Run(d_data, is_double, true, nrow, ncol, d_out, nullptr);
-  HIPCHECK(hipStreamSynchronize(nullptr));
-  ++g_device_predictions;
-}
-
-namespace {
-
 // the scatter of CSR rows [0, rows) (indptr on the device, entry_base = its first value) into d_mat
 void RunCsrToSlots(const DeviceForest& forest, const void* d_indptr, bool indptr_is_64, const int32_t* d_indices,
                    const void* d_data, bool is_double, int64_t rows, int64_t entry_base, int64_t entries,
@@ -308,166 +201,6 @@ void RunCsrToSlots(const DeviceForest& forest, const void* d_indptr, bool indptr
   dev::CsrToSlots(c, s);
   HIPCHECK(hipGetLastError());
 }
-
-}  // namespace
-
-bool GBDT::PredictCSROnDevice(const void* indptr, bool indptr_is_64, const int32_t* indices, const void* data,
-                              bool is_double, int64_t nindptr, int64_t nelem, int start_iteration, int num_iteration,
-                              DevicePredictKind kind, double* out) {
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return false;
-  const int64_t nrow = nindptr - 1;
-  if (num_tree_per_iteration_ > dev::kMaxPredClasses || nrow <= 0) return false;
-  // (rows are copied by their indptr entries: a matrix whose indptr does not ascend within the
-  // stored entries is left to the host)
-  const SparsePtr ptr{indptr, indptr_is_64};
-  if (!PointerValid(ptr, nrow, nelem)) return false;
-  const int ntpi = num_tree_per_iteration_;
-  const int num_features = max_feature_idx_ + 1;
-  const std::vector<const Tree*> trees = PredictWindowTrees(start_iteration, num_iteration);
-  hipStream_t s;
-  HIPCHECK(hipStreamCreateWithFlags(&s, hipStreamNonBlocking));
-  bool ran = false;
-  {
-    DeviceForest forest;
-    if (forest.Upload(trees, ntpi, num_features, kind, s, true)) {
-      const size_t elem = is_double ? 8 : 4;
-      const size_t ptr_b = indptr_is_64 ? 8 : 4;
-      const int nslot = forest.NumSlots();
-      const int64_t per_out = forest.OutPerRow();
-      // rows per chunk: the compact matrix, the output, the accumulator tiles and the chunk's
-      // stored entries within most of the free memory
-      size_t free_b = 0, total_b = 0;
-      HIPCHECK(hipMemGetInfo(&free_b, &total_b));
-      const size_t per_row = static_cast<size_t>(nslot) * elem + static_cast<size_t>(per_out) * sizeof(double) + ptr_b;
-      const size_t per_entry = sizeof(int32_t) + elem;
-      const size_t budget = free_b - free_b / 5;
-      const size_t fixed = forest.ScratchBytes(nrow) + ptr_b;
-      int64_t chunk = budget > fixed ? static_cast<int64_t>((budget - fixed) / per_row) : 0;
-      chunk = std::max<int64_t>(dev::kShapLanes, chunk / dev::kShapLanes * dev::kShapLanes);
-      const int forced = tuning::Int(tuning::Knob::PredictChunkRows, 0);
-      if (forced > 0) chunk = forced;
-      chunk = std::min(chunk, nrow);
-      // the most stored entries of a chunk
-      auto most_entries = [&](int64_t rows) {
-        int64_t most = 0;
-        for (int64_t r0 = 0; r0 < nrow; r0 += rows) {
-          most = std::max(most, ptr[std::min(r0 + rows, nrow)] - ptr[r0]);
-        }
-        return most;
-      };
-      int64_t entries = most_entries(chunk);
-      bool fits = true;
-      while (forced <= 0 && fixed + static_cast<size_t>(chunk) * per_row + static_cast<size_t>(entries) * per_entry > budget) {
-        if (chunk <= dev::kShapLanes) {
-          fits = false;
-          break;
-        }
-        chunk = std::max<int64_t>(dev::kShapLanes, chunk / 2 / dev::kShapLanes * dev::kShapLanes);
-        entries = most_entries(chunk);
-      }
-      if (fits) {
-        DeviceBuffers b;
-        void* d_indptr = b.Alloc(static_cast<size_t>(chunk + 1) * ptr_b);
-        int32_t* d_indices = static_cast<int32_t*>(b.Alloc(static_cast<size_t>(entries) * sizeof(int32_t)));
-        void* d_data = b.Alloc(static_cast<size_t>(entries) * elem);
-        void* d_mat = b.Alloc(static_cast<size_t>(chunk) * nslot * elem);
-        double* d_out = static_cast<double*>(b.Alloc(static_cast<size_t>(chunk) * per_out * sizeof(double)));
-        const bool convert = kind == DevicePredictKind::Normal;
-        std::vector<double> raw_out(convert ? static_cast<size_t>(nrow) * per_out : 0);
-        double* host_out = convert ? raw_out.data() : out;
-        for (int64_t r0 = 0; r0 < nrow; r0 += chunk) {
-          const int64_t rows = std::min(chunk, nrow - r0);
-          const int64_t e0 = ptr[r0];
-          const int64_t ne = ptr[r0 + rows] - e0;
-          HIPCHECK(hipMemcpyAsync(d_indptr, static_cast<const char*>(indptr) + static_cast<size_t>(r0) * ptr_b,
-                                  static_cast<size_t>(rows + 1) * ptr_b, hipMemcpyHostToDevice, s));
-          if (ne > 0) {
-            HIPCHECK(hipMemcpyAsync(d_indices, indices + e0, static_cast<size_t>(ne) * sizeof(int32_t),
-                                    hipMemcpyHostToDevice, s));
-            HIPCHECK(hipMemcpyAsync(d_data, static_cast<const char*>(data) + static_cast<size_t>(e0) * elem,
-                                    static_cast<size_t>(ne) * elem, hipMemcpyHostToDevice, s));
-          }
-          RunCsrToSlots(forest, d_indptr, indptr_is_64, d_indices, d_data, is_double, rows, e0, ne, num_features,
-                        d_mat, s);
-          forest.Run(d_mat, is_double, false, rows, nslot, d_out, s);
-          HIPCHECK(hipMemcpyAsync(host_out + r0 * per_out, d_out, static_cast<size_t>(rows) * per_out * sizeof(double),
-                                  hipMemcpyDeviceToHost, s));
-          HIPCHECK(hipStreamSynchronize(s));
-        }
-        ran = true;
-        ++g_device_predictions;
-        if (convert) {
-#pragma omp parallel for schedule(static)
-          for (int64_t r = 0; r < nrow; ++r) {
-            double* o = out + r * ntpi;
-            std::memcpy(o, raw_out.data() + r * ntpi, sizeof(double) * ntpi);
-            if (average_output_) {
-              for (int k = 0; k < ntpi; ++k) o[k] /= num_iteration_for_pred_;
-            }
-            if (objective_ != nullptr) objective_->ConvertOutput(o, o);
-          }
-        }
-      }
-    }
-  }
-  HIPCHECK(hipStreamDestroy(s));
-  return ran;
-}
-
-void GBDT::PredictCSRDeviceBuffers(const void* d_indptr, bool indptr_is_64, const int32_t* d_indices,
-                                   const void* d_data, bool is_double, int64_t nrow, int64_t nelem,
-                                   int start_iteration, int num_iteration, DevicePredictKind kind, double* d_out,
-                                   int64_t out_len) {
-  if (kind == DevicePredictKind::Normal) Log::Fatal("device buffers are predicted as raw scores, leaf indices or contributions");
-  if (num_tree_per_iteration_ > dev::kMaxPredClasses) {
-    Log::Fatal("forest prediction on the device handles at most %d trees per iteration", dev::kMaxPredClasses);
-  }
-  if (nrow < 0 || nelem < 0) Log::Fatal("CSR device buffers: %lld rows, %lld entries", static_cast<long long>(nrow), static_cast<long long>(nelem));
-  const std::vector<const Tree*> trees = PredictWindowTrees(start_iteration, num_iteration);
-  DeviceForest forest;
-  if (!forest.Upload(trees, num_tree_per_iteration_, max_feature_idx_ + 1, kind, nullptr, true)) {
-    Log::Fatal("contributions on the device need paths of at most %d distinct features and data counts on every node",
-               dev::kShapMaxPathLen - 1);
-  }
-  if (out_len != nrow * forest.OutPerRow()) {
-    Log::Fatal("output holds %lld doubles, the prediction has %lld", static_cast<long long>(out_len),
-               static_cast<long long>(nrow * forest.OutPerRow()));
-  }
-  if (nrow > 0) {
-    DeviceBuffers b;
-    void* d_mat = b.Alloc(static_cast<size_t>(nrow) * forest.NumSlots() * (is_double ? 8 : 4));
-    // (the rows are clamped to nelem entries in the kernel: indptr stays on the device)
-    RunCsrToSlots(forest, d_indptr, indptr_is_64, d_indices, d_data, is_double, nrow, 0, nelem, max_feature_idx_ + 1,
-                  d_mat, nullptr);
-    forest.Run(d_mat, is_double, false, nrow, forest.NumSlots(), d_out, nullptr);
-    HIPCHECK(hipStreamSynchronize(nullptr));
-  }
-  ++g_device_predictions;
-}
-
-void GBDT::CsrToSlotsOnHost(const void* indptr, bool indptr_is_64, const int32_t* indices, const void* data,
-                            bool is_double, int64_t nindptr, int64_t nelem, int start_iteration, int num_iteration,
-                            int32_t* num_used, int32_t* used, void* matrix) {
-  const std::vector<const Tree*> trees = PredictWindowTrees(start_iteration, num_iteration);
-  FlatForest flat;
-  flat.Build(trees);
-  FeatureSlots slots;
-  const int nf = max_feature_idx_ + 1;
-  slots.Build(flat, nf);
-  const int ns = static_cast<int>(slots.used.size());
-  *num_used = ns;
-  if (used != nullptr) std::copy(slots.used.begin(), slots.used.end(), used);
-  if (matrix == nullptr || nindptr <= 1) return;
-  const int64_t rows = nindptr - 1;
-  const int32_t* so = slots.slot_of.data();
-  DispatchSparse(indptr_is_64, is_double, indptr, data, [&](auto* ptr, auto* val) {
-    using T = std::decay_t<decltype(*val)>;
-    dev::EvalCsrToSlots(ptr, 0, indices, val, rows, nelem, so, nf, ns, static_cast<T*>(matrix));
-  });
-}
-
-namespace {
 
 // the scatter arguments of CSC arrays on the device; `d_ascending` holds a word per slot
 dev::CscSlotsArgs CscArgs(const DeviceForest& forest, const void* d_col_ptr, bool col_ptr_is_64,
@@ -500,83 +233,195 @@ void RunCscToSlots(dev::CscSlotsArgs c, int64_t row0, int64_t rows, void* d_mat,
   HIPCHECK(hipGetLastError());
 }
 
+// A row source is what differs between the input layouts under GBDT::PredictChunksOnDevice:
+//   kSlots       the forest walks a compact matrix of the features it splits on
+//   Measure      the device bytes of the input, next to the output and the accumulator tiles
+//   MostEntries  the most stored entries staged with a chunk of `rows` rows (0: none are)
+//   Prepare      after the plan: allocates / uploads into `b` what lives for the whole call
+//   Stage        rows [r0, r0 + rows) onto the device, on the stream: the matrix the forest walks
+struct SourceBytes {
+  size_t fixed, per_row, per_entry;
+};
+struct ChunkMatrix {
+  const void* data;
+  bool row_major;
+  int ncol;
+};
+
+struct DenseRows {
+  const void* data;
+  int64_t nrow;
+  int ncol;
+  size_t elem;  // bytes of a value: float32 / float64
+  bool row_major;
+  void* d_data = nullptr;
+
+  static constexpr bool kSlots = false;
+  SourceBytes Measure(const DeviceForest&) { return {0, static_cast<size_t>(ncol) * elem, 0}; }
+  int64_t MostEntries(int64_t) const { return 0; }
+  void Prepare(const DeviceForest&, const PredictChunkPlan& plan, DeviceBuffers* b, hipStream_t) {
+    d_data = b->Alloc(static_cast<size_t>(plan.chunk) * ncol * elem);
+  }
+  ChunkMatrix Stage(const DeviceForest&, int64_t r0, int64_t rows, hipStream_t s) {
+    const char* src = static_cast<const char*>(data);
+    if (row_major) {
+      HIPCHECK(hipMemcpyAsync(d_data, src + static_cast<size_t>(r0) * ncol * elem,
+                              static_cast<size_t>(rows) * ncol * elem, hipMemcpyHostToDevice, s));
+    } else if (rows == nrow) {
+      HIPCHECK(hipMemcpyAsync(d_data, src, static_cast<size_t>(rows) * ncol * elem, hipMemcpyHostToDevice, s));
+    } else {  // the chunk's rows of every column, compacted to a column stride of `rows`
+      HIPCHECK(hipMemcpy2DAsync(d_data, static_cast<size_t>(rows) * elem, src + static_cast<size_t>(r0) * elem,
+                                static_cast<size_t>(nrow) * elem, static_cast<size_t>(rows) * elem, ncol,
+                                hipMemcpyHostToDevice, s));
+    }
+    return {d_data, row_major, ncol};
+  }
+};
+
+// a chunk's rows are copied by their indptr entries and scattered into the compact matrix
+struct CsrRows {
+  SparsePtr ptr;
+  const int32_t* indices;
+  const void* data;
+  int64_t nrow;
+  int num_features;
+  size_t elem;
+  void *d_indptr = nullptr, *d_data = nullptr, *d_mat = nullptr;
+  int32_t* d_indices = nullptr;
+
+  static constexpr bool kSlots = true;
+  size_t PtrBytes() const { return ptr.is_64 ? 8 : 4; }
+  SourceBytes Measure(const DeviceForest& f) {
+    return {PtrBytes(), static_cast<size_t>(f.NumSlots()) * elem + PtrBytes(), sizeof(int32_t) + elem};
+  }
+  int64_t MostEntries(int64_t rows) const { return MostChunkEntries(ptr, nrow, rows); }
+  void Prepare(const DeviceForest& f, const PredictChunkPlan& plan, DeviceBuffers* b, hipStream_t) {
+    d_indptr = b->Alloc(static_cast<size_t>(plan.chunk + 1) * PtrBytes());
+    d_indices = static_cast<int32_t*>(b->Alloc(static_cast<size_t>(plan.entries) * sizeof(int32_t)));
+    d_data = b->Alloc(static_cast<size_t>(plan.entries) * elem);
+    d_mat = b->Alloc(static_cast<size_t>(plan.chunk) * f.NumSlots() * elem);
+  }
+  ChunkMatrix Stage(const DeviceForest& f, int64_t r0, int64_t rows, hipStream_t s) {
+    const int64_t e0 = ptr[r0];
+    const int64_t ne = ptr[r0 + rows] - e0;
+    HIPCHECK(hipMemcpyAsync(d_indptr, static_cast<const char*>(ptr.p) + static_cast<size_t>(r0) * PtrBytes(),
+                            static_cast<size_t>(rows + 1) * PtrBytes(), hipMemcpyHostToDevice, s));
+    if (ne > 0) {
+      HIPCHECK(hipMemcpyAsync(d_indices, indices + e0, static_cast<size_t>(ne) * sizeof(int32_t),
+                              hipMemcpyHostToDevice, s));
+      HIPCHECK(hipMemcpyAsync(d_data, static_cast<const char*>(data) + static_cast<size_t>(e0) * elem,
+                              static_cast<size_t>(ne) * elem, hipMemcpyHostToDevice, s));
+    }
+    RunCsrToSlots(f, d_indptr, ptr.is_64, d_indices, d_data, elem == 8, rows, e0, ne, num_features, d_mat, s);
+    return {d_mat, false, f.NumSlots()};
+  }
+};
+
+// the stored entries of the columns the trees split on stay on the device for the call; a chunk's
+// rows are scattered from them
+struct CscRows {
+  SparsePtr col_ptr;
+  const int32_t* indices;
+  const void* data;
+  int64_t ncol;
+  size_t elem;
+  // the stored entries of the used columns, packed slot after slot: a pointer of nslot + 1
+  // entries over them, and the runs of adjacent used columns, each one copy
+  std::vector<int64_t> ptr;
+  std::vector<ColumnRun> runs;
+  std::vector<int32_t> slot_col;
+  dev::CscSlotsArgs c{};
+  void* d_mat = nullptr;
+
+  static constexpr bool kSlots = true;
+  SourceBytes Measure(const DeviceForest& f) {
+    const int nslot = f.NumSlots();
+    PackColumnRuns(f.Used(), col_ptr, ncol, &runs, &ptr);
+    return {static_cast<size_t>(ptr[nslot]) * (sizeof(int32_t) + elem) +
+                (static_cast<size_t>(nslot) + 1) * (sizeof(int64_t) + 2 * sizeof(int32_t)),
+            static_cast<size_t>(nslot) * elem, 0};
+  }
+  int64_t MostEntries(int64_t) const { return 0; }
+  void Prepare(const DeviceForest& f, const PredictChunkPlan& plan, DeviceBuffers* b, hipStream_t s) {
+    const int nslot = f.NumSlots();
+    const int64_t entries = ptr[nslot];
+    slot_col.assign(nslot, -1);
+    for (int k = 0; k < nslot; ++k) {
+      if (f.Used()[k] < ncol) slot_col[k] = k;  // (else a matrix narrower than the model: it reads 0)
+    }
+    const int64_t* d_ptr = b->Upload(ptr, s);
+    const int32_t* d_slot_col = b->Upload(slot_col, s);
+    int32_t* d_indices = static_cast<int32_t*>(b->Alloc(static_cast<size_t>(entries) * sizeof(int32_t)));
+    char* d_data = static_cast<char*>(b->Alloc(static_cast<size_t>(entries) * elem));
+    uint32_t* d_ascending = static_cast<uint32_t*>(b->Alloc(static_cast<size_t>(nslot) * sizeof(uint32_t)));
+    // (every run where it lies: packing the runs on the host first, for two large copies, was
+    // measured slower at 266 runs -- profiles/r12_device_csc_predict.md)
+    for (const ColumnRun& r : runs) {
+      HIPCHECK(hipMemcpyAsync(d_indices + r.dst, indices + r.src, static_cast<size_t>(r.len) * sizeof(int32_t),
+                              hipMemcpyHostToDevice, s));
+      HIPCHECK(hipMemcpyAsync(d_data + static_cast<size_t>(r.dst) * elem,
+                              static_cast<const char*>(data) + static_cast<size_t>(r.src) * elem,
+                              static_cast<size_t>(r.len) * elem, hipMemcpyHostToDevice, s));
+    }
+    c = CscArgs(f, d_ptr, true, d_slot_col, d_indices, d_data, elem == 8, entries, d_ascending);
+    dev::CscColumnOrder(c, s);
+    HIPCHECK(hipGetLastError());
+    d_mat = b->Alloc(static_cast<size_t>(plan.chunk) * nslot * elem);
+  }
+  ChunkMatrix Stage(const DeviceForest&, int64_t r0, int64_t rows, hipStream_t s) {
+    RunCscToSlots(c, r0, rows, d_mat, s);
+    return {d_mat, false, c.num_slots};
+  }
+};
+
 }  // namespace
 
-bool GBDT::PredictCSCOnDevice(const void* col_ptr, bool col_ptr_is_64, const int32_t* indices, const void* data,
-                              bool is_double, int64_t ncol_ptr, int64_t nelem, int64_t num_row, int start_iteration,
-                              int num_iteration, DevicePredictKind kind, double* out) {
+std::vector<const Tree*> GBDT::PredictWindowTrees(int start_iteration, int num_iteration) {
+  InitPredict(start_iteration, num_iteration, false);
+  const int t0 = start_iteration_for_pred_ * num_tree_per_iteration_;
+  const int nt = num_iteration_for_pred_ * num_tree_per_iteration_;
+  std::vector<const Tree*> trees(nt);
+  for (int i = 0; i < nt; ++i) trees[i] = models_[t0 + i].get();
+  return trees;
+}
+
+template <typename Source>
+bool GBDT::PredictChunksOnDevice(Source* src, int64_t nrow, int start_iteration, int num_iteration,
+                                 DevicePredictKind kind, double* out) {
   int ndev = 0;
   if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return false;
-  const int64_t ncol = ncol_ptr - 1;
-  if (num_tree_per_iteration_ > dev::kMaxPredClasses || num_row <= 0 || ncol < 0 || nelem < 0) return false;
-  // (columns are copied by their pointer entries: a matrix whose pointer does not ascend within
-  // the stored entries is left to the host)
-  if (!PointerValid(SparsePtr{col_ptr, col_ptr_is_64}, ncol, nelem)) return false;
+  if (num_tree_per_iteration_ > dev::kMaxPredClasses || nrow <= 0) return false;
   const int ntpi = num_tree_per_iteration_;
-  const int num_features = max_feature_idx_ + 1;
+  // (the forest is rebuilt per call: trees may have been edited in place)
   const std::vector<const Tree*> trees = PredictWindowTrees(start_iteration, num_iteration);
   hipStream_t s;
   HIPCHECK(hipStreamCreateWithFlags(&s, hipStreamNonBlocking));
   bool ran = false;
   {
     DeviceForest forest;
-    if (forest.Upload(trees, ntpi, num_features, kind, s, true)) {
-      const size_t elem = is_double ? 8 : 4;
-      const int nslot = forest.NumSlots();
+    if (forest.Upload(trees, ntpi, max_feature_idx_ + 1, kind, s, Source::kSlots)) {
       const int64_t per_out = forest.OutPerRow();
-      // the stored entries of the used columns, packed slot after slot: a pointer of nslot + 1
-      // entries over them, and the runs of adjacent used columns, each one copy
-      std::vector<int64_t> ptr;
-      std::vector<ColumnRun> runs;
-      PackColumnRuns(forest.Used(), SparsePtr{col_ptr, col_ptr_is_64}, ncol, &runs, &ptr);
-      std::vector<int32_t> slot_col(nslot, -1);
-      for (int k = 0; k < nslot; ++k) {
-        if (forest.Used()[k] < ncol) slot_col[k] = k;  // (else a matrix narrower than the model: it reads 0)
-      }
-      const int64_t entries = ptr[nslot];
-      // rows per chunk: the compact matrix, the output and the accumulator tiles within most of
-      // the free memory, next to the entries, which stay on the device for the call
+      const SourceBytes in = src->Measure(forest);
+      // rows per chunk (predict_chunks.h): input, output and the accumulator tiles within most of
+      // the free memory
       size_t free_b = 0, total_b = 0;
       HIPCHECK(hipMemGetInfo(&free_b, &total_b));
-      const size_t per_row = static_cast<size_t>(nslot) * elem + static_cast<size_t>(per_out) * sizeof(double);
-      const size_t budget = free_b - free_b / 5;
-      const size_t fixed = forest.ScratchBytes(num_row) + static_cast<size_t>(entries) * (sizeof(int32_t) + elem) +
-                           (static_cast<size_t>(nslot) + 1) * (sizeof(int64_t) + 2 * sizeof(int32_t));
-      const bool fits = fixed + static_cast<size_t>(dev::kShapLanes) * per_row <= budget;
-      if (fits) {
-        int64_t chunk = static_cast<int64_t>((budget - fixed) / per_row);
-        chunk = std::max<int64_t>(dev::kShapLanes, chunk / dev::kShapLanes * dev::kShapLanes);
-        const int forced = tuning::Int(tuning::Knob::PredictChunkRows, 0);
-        if (forced > 0) chunk = forced;
-        chunk = std::min(chunk, num_row);
+      const PredictChunkPlan plan = PlanPredictChunks(
+          nrow, free_b - free_b / 5, forest.ScratchBytes(nrow) + in.fixed,
+          in.per_row + static_cast<size_t>(per_out) * sizeof(double), in.per_entry,
+          tuning::Int(tuning::Knob::PredictChunkRows, 0), dev::kShapLanes,
+          [&](int64_t rows) { return src->MostEntries(rows); });
+      if (plan.fits) {
         DeviceBuffers b;
-        const int64_t* d_ptr = b.Upload(ptr, s);
-        const int32_t* d_slot_col = b.Upload(slot_col, s);
-        int32_t* d_indices = static_cast<int32_t*>(b.Alloc(static_cast<size_t>(entries) * sizeof(int32_t)));
-        char* d_data = static_cast<char*>(b.Alloc(static_cast<size_t>(entries) * elem));
-        uint32_t* d_ascending = static_cast<uint32_t*>(b.Alloc(static_cast<size_t>(nslot) * sizeof(uint32_t)));
-        // (every run where it lies: packing the runs on the host first, for two large copies, was
-        // measured slower at 266 runs -- profiles/r12_device_csc_predict.md)
-        for (const ColumnRun& r : runs) {
-          HIPCHECK(hipMemcpyAsync(d_indices + r.dst, indices + r.src, static_cast<size_t>(r.len) * sizeof(int32_t),
-                                  hipMemcpyHostToDevice, s));
-          HIPCHECK(hipMemcpyAsync(d_data + static_cast<size_t>(r.dst) * elem,
-                                  static_cast<const char*>(data) + static_cast<size_t>(r.src) * elem,
-                                  static_cast<size_t>(r.len) * elem, hipMemcpyHostToDevice, s));
-        }
-        const dev::CscSlotsArgs c = CscArgs(forest, d_ptr, true, d_slot_col, d_indices, d_data, is_double, entries,
-                                            d_ascending);
-        dev::CscColumnOrder(c, s);
-        HIPCHECK(hipGetLastError());
-        void* d_mat = b.Alloc(static_cast<size_t>(chunk) * nslot * elem);
-        double* d_out = static_cast<double*>(b.Alloc(static_cast<size_t>(chunk) * per_out * sizeof(double)));
+        src->Prepare(forest, plan, &b, s);
+        double* d_out = static_cast<double*>(b.Alloc(static_cast<size_t>(plan.chunk) * per_out * sizeof(double)));
         const bool convert = kind == DevicePredictKind::Normal;
-        std::vector<double> raw_out(convert ? static_cast<size_t>(num_row) * per_out : 0);
+        std::vector<double> raw_out(convert ? static_cast<size_t>(nrow) * per_out : 0);
         double* host_out = convert ? raw_out.data() : out;
-        for (int64_t r0 = 0; r0 < num_row; r0 += chunk) {
-          const int64_t rows = std::min(chunk, num_row - r0);
-          RunCscToSlots(c, r0, rows, d_mat, s);
-          forest.Run(d_mat, is_double, false, rows, nslot, d_out, s);
+        for (int64_t r0 = 0; r0 < nrow; r0 += plan.chunk) {
+          const int64_t rows = std::min(plan.chunk, nrow - r0);
+          const ChunkMatrix m = src->Stage(forest, r0, rows, s);
+          forest.Run(m.data, src->elem == 8, m.row_major, rows, m.ncol, d_out, s);
           HIPCHECK(hipMemcpyAsync(host_out + r0 * per_out, d_out, static_cast<size_t>(rows) * per_out * sizeof(double),
                                   hipMemcpyDeviceToHost, s));
           HIPCHECK(hipStreamSynchronize(s));
@@ -585,7 +430,7 @@ bool GBDT::PredictCSCOnDevice(const void* col_ptr, bool col_ptr_is_64, const int
         ++g_device_predictions;
         if (convert) {
 #pragma omp parallel for schedule(static)
-          for (int64_t r = 0; r < num_row; ++r) {
+          for (int64_t r = 0; r < nrow; ++r) {
             double* o = out + r * ntpi;
             std::memcpy(o, raw_out.data() + r * ntpi, sizeof(double) * ntpi);
             if (average_output_) {
@@ -601,28 +446,100 @@ bool GBDT::PredictCSCOnDevice(const void* col_ptr, bool col_ptr_is_64, const int
   return ran;
 }
 
-void GBDT::PredictCSCDeviceBuffers(const void* d_col_ptr, bool col_ptr_is_64, const int32_t* d_indices,
-                                   const void* d_data, bool is_double, int64_t ncol, int64_t nelem, int64_t nrow,
-                                   int start_iteration, int num_iteration, DevicePredictKind kind, double* d_out,
-                                   int64_t out_len) {
+template <typename Forest>
+void GBDT::UploadForDeviceBuffers(Forest* forest, DevicePredictKind kind, bool slots, int64_t nrow, int64_t out_len,
+                                  int start_iteration, int num_iteration) {
   if (kind == DevicePredictKind::Normal) Log::Fatal("device buffers are predicted as raw scores, leaf indices or contributions");
   if (num_tree_per_iteration_ > dev::kMaxPredClasses) {
     Log::Fatal("forest prediction on the device handles at most %d trees per iteration", dev::kMaxPredClasses);
   }
+  const std::vector<const Tree*> trees = PredictWindowTrees(start_iteration, num_iteration);
+  if (!forest->Upload(trees, num_tree_per_iteration_, max_feature_idx_ + 1, kind, nullptr, slots)) {
+    Log::Fatal("contributions on the device need paths of at most %d distinct features and data counts on every node",
+               dev::kShapMaxPathLen - 1);
+  }
+  if (out_len != nrow * forest->OutPerRow()) {
+    Log::Fatal("output holds %lld doubles, the prediction has %lld", static_cast<long long>(out_len),
+               static_cast<long long>(nrow * forest->OutPerRow()));
+  }
+}
+
+bool GBDT::PredictDenseOnDevice(const void* data, bool is_double, int64_t nrow, int ncol, bool row_major,
+                                int start_iteration, int num_iteration, DevicePredictKind kind, double* out) {
+  // (a matrix narrower than the model, let through by predict_disable_shape_check: the kernels index
+  // a row by the model's features, and the host predictor reads the absent columns as 0)
+  if (ncol <= max_feature_idx_) return false;
+  DenseRows src{data, nrow, ncol, is_double ? 8u : 4u, row_major};
+  return PredictChunksOnDevice(&src, nrow, start_iteration, num_iteration, kind, out);
+}
+
+void GBDT::PredictDeviceBuffers(const void* d_data, bool is_double, int64_t nrow, int ncol, int start_iteration,
+                                int num_iteration, DevicePredictKind kind, double* d_out, int64_t out_len) {
+  if (ncol != max_feature_idx_ + 1) {
+    Log::Fatal("The number of features in data (%d) is not the same as it was in training data (%d).", ncol,
+               max_feature_idx_ + 1);
+  }
+  DeviceForest forest;
+  UploadForDeviceBuffers(&forest, kind, false, nrow, out_len, start_iteration, num_iteration);
+  if (nrow > 0) forest.Run(d_data, is_double, true, nrow, ncol, d_out, nullptr);
+  HIPCHECK(hipStreamSynchronize(nullptr));
+  ++g_device_predictions;
+}
+
+bool GBDT::PredictCSROnDevice(const void* indptr, bool indptr_is_64, const int32_t* indices, const void* data,
+                              bool is_double, int64_t nindptr, int64_t nelem, int start_iteration, int num_iteration,
+                              DevicePredictKind kind, double* out) {
+  const int64_t nrow = nindptr - 1;
+  // (rows are copied by their indptr entries: a matrix whose indptr does not ascend within the
+  // stored entries is left to the host)
+  const SparsePtr ptr{indptr, indptr_is_64};
+  if (nrow <= 0 || !PointerValid(ptr, nrow, nelem)) return false;
+  CsrRows src{ptr, indices, data, nrow, max_feature_idx_ + 1, is_double ? 8u : 4u};
+  return PredictChunksOnDevice(&src, nrow, start_iteration, num_iteration, kind, out);
+}
+
+void GBDT::PredictCSRDeviceBuffers(const void* d_indptr, bool indptr_is_64, const int32_t* d_indices,
+                                   const void* d_data, bool is_double, int64_t nrow, int64_t nelem,
+                                   int start_iteration, int num_iteration, DevicePredictKind kind, double* d_out,
+                                   int64_t out_len) {
+  if (nrow < 0 || nelem < 0) Log::Fatal("CSR device buffers: %lld rows, %lld entries", static_cast<long long>(nrow), static_cast<long long>(nelem));
+  DeviceForest forest;
+  UploadForDeviceBuffers(&forest, kind, true, nrow, out_len, start_iteration, num_iteration);
+  if (nrow > 0) {
+    DeviceBuffers b;
+    void* d_mat = b.Alloc(static_cast<size_t>(nrow) * forest.NumSlots() * (is_double ? 8 : 4));
+    // (the rows are clamped to nelem entries in the kernel: indptr stays on the device)
+    RunCsrToSlots(forest, d_indptr, indptr_is_64, d_indices, d_data, is_double, nrow, 0, nelem, max_feature_idx_ + 1,
+                  d_mat, nullptr);
+    forest.Run(d_mat, is_double, false, nrow, forest.NumSlots(), d_out, nullptr);
+    HIPCHECK(hipStreamSynchronize(nullptr));
+  }
+  ++g_device_predictions;
+}
+
+bool GBDT::PredictCSCOnDevice(const void* col_ptr, bool col_ptr_is_64, const int32_t* indices, const void* data,
+                              bool is_double, int64_t ncol_ptr, int64_t nelem, int64_t num_row, int start_iteration,
+                              int num_iteration, DevicePredictKind kind, double* out) {
+  const int64_t ncol = ncol_ptr - 1;
+  if (num_row <= 0 || ncol < 0 || nelem < 0) return false;
+  // (columns are copied by their pointer entries: a matrix whose pointer does not ascend within
+  // the stored entries is left to the host)
+  const SparsePtr ptr{col_ptr, col_ptr_is_64};
+  if (!PointerValid(ptr, ncol, nelem)) return false;
+  CscRows src{ptr, indices, data, ncol, is_double ? 8u : 4u};
+  return PredictChunksOnDevice(&src, num_row, start_iteration, num_iteration, kind, out);
+}
+
+void GBDT::PredictCSCDeviceBuffers(const void* d_col_ptr, bool col_ptr_is_64, const int32_t* d_indices,
+                                   const void* d_data, bool is_double, int64_t ncol, int64_t nelem, int64_t nrow,
+                                   int start_iteration, int num_iteration, DevicePredictKind kind, double* d_out,
+                                   int64_t out_len) {
   if (nrow < 0 || nelem < 0 || ncol < 0) {
     Log::Fatal("CSC device buffers: %lld rows, %lld columns, %lld entries", static_cast<long long>(nrow),
                static_cast<long long>(ncol), static_cast<long long>(nelem));
   }
-  const std::vector<const Tree*> trees = PredictWindowTrees(start_iteration, num_iteration);
   DeviceForest forest;
-  if (!forest.Upload(trees, num_tree_per_iteration_, max_feature_idx_ + 1, kind, nullptr, true)) {
-    Log::Fatal("contributions on the device need paths of at most %d distinct features and data counts on every node",
-               dev::kShapMaxPathLen - 1);
-  }
-  if (out_len != nrow * forest.OutPerRow()) {
-    Log::Fatal("output holds %lld doubles, the prediction has %lld", static_cast<long long>(out_len),
-               static_cast<long long>(nrow * forest.OutPerRow()));
-  }
+  UploadForDeviceBuffers(&forest, kind, true, nrow, out_len, start_iteration, num_iteration);
   if (nrow > 0) {
     const int nslot = forest.NumSlots();
     // (the full pointer stays on the device: a slot names its feature's column, if the matrix has it)
@@ -643,6 +560,27 @@ void GBDT::PredictCSCDeviceBuffers(const void* d_col_ptr, bool col_ptr_is_64, co
     HIPCHECK(hipStreamSynchronize(nullptr));
   }
   ++g_device_predictions;
+}
+
+void GBDT::CsrToSlotsOnHost(const void* indptr, bool indptr_is_64, const int32_t* indices, const void* data,
+                            bool is_double, int64_t nindptr, int64_t nelem, int start_iteration, int num_iteration,
+                            int32_t* num_used, int32_t* used, void* matrix) {
+  const std::vector<const Tree*> trees = PredictWindowTrees(start_iteration, num_iteration);
+  FlatForest flat;
+  flat.Build(trees);
+  FeatureSlots slots;
+  const int nf = max_feature_idx_ + 1;
+  slots.Build(flat, nf);
+  const int ns = static_cast<int>(slots.used.size());
+  *num_used = ns;
+  if (used != nullptr) std::copy(slots.used.begin(), slots.used.end(), used);
+  if (matrix == nullptr || nindptr <= 1) return;
+  const int64_t rows = nindptr - 1;
+  const int32_t* so = slots.slot_of.data();
+  DispatchSparse(indptr_is_64, is_double, indptr, data, [&](auto* ptr, auto* val) {
+    using T = std::decay_t<decltype(*val)>;
+    dev::EvalCsrToSlots(ptr, 0, indices, val, rows, nelem, so, nf, ns, static_cast<T*>(matrix));
+  });
 }
 
 void GBDT::CscToSlotsOnHost(const void* col_ptr, bool col_ptr_is_64, const int32_t* indices, const void* data,

@@ -36,11 +36,13 @@
 #include "lgbm_amd/random.h"
 #include "lgbm_amd/sparse_ptr.h"
 #include "lgbm_amd/tuning.h"
+#include "../boosting/predict_chunks.h"
 #include "../device/csc_bins.h"
 #include "../device/kernels.h"
 #include "../device/refit_quant.h"
 #include "../device/score_convert.h"
 #include "../treelearner/growth_limits.h"
+#include "booster_device_buffers.h"
 
 using namespace lgbm_amd;
 
@@ -521,17 +523,11 @@ class Booster {
   bool PredictDenseOnDevice(const void* data, int data_type, int32_t nrow, int32_t ncol, int is_row_major,
                             int predict_type, int start_iteration, int num_iteration, const Config& cfg, double* out,
                             int64_t* out_len) {
-    DevicePredictKind kind;
-    if (!DevicePredictGate(data_type, nrow, ncol, predict_type, cfg, &kind)) return false;
-    std::unique_lock<std::shared_mutex> l(mu_);
-    if (!boosting_->PredictDenseOnDevice(data, data_type == C_API_DTYPE_FLOAT64, nrow, ncol, is_row_major != 0,
-                                         start_iteration, num_iteration, kind, out)) {
-      return false;
-    }
-    *out_len = static_cast<int64_t>(nrow) *
-               boosting_->NumPredictOneRow(start_iteration, num_iteration, kind == DevicePredictKind::Leaf,
-                                           kind == DevicePredictKind::Contrib);
-    return true;
+    auto call = [&](DevicePredictKind kind) {
+      return boosting_->PredictDenseOnDevice(data, data_type == C_API_DTYPE_FLOAT64, nrow, ncol, is_row_major != 0,
+                                             start_iteration, num_iteration, kind, out);
+    };
+    return PredictOnDevice(data_type, nrow, ncol, predict_type, start_iteration, num_iteration, cfg, out_len, call);
   }
 
   // whether a host matrix of nrow x ncol goes to the device (dense, CSR and CSC alike)
@@ -547,6 +543,20 @@ class Booster {
     return true;
   }
 
+  // a host matrix through the gate to `call(kind)`, one of the GBDT's Predict*OnDevice under the
+  // exclusive lock; false: the host predicts
+  template <typename Call>
+  bool PredictOnDevice(int data_type, int64_t nrow, int64_t ncol, int predict_type, int start_iteration,
+                       int num_iteration, const Config& cfg, int64_t* out_len, Call&& call) {
+    DevicePredictKind kind;
+    if (!DevicePredictGate(data_type, nrow, ncol, predict_type, cfg, &kind)) return false;
+    std::unique_lock<std::shared_mutex> l(mu_);
+    if (!call(kind)) return false;
+    *out_len = nrow * boosting_->NumPredictOneRow(start_iteration, num_iteration, kind == DevicePredictKind::Leaf,
+                                                  kind == DevicePredictKind::Contrib);
+    return true;
+  }
+
   // CSR rows under the same gate: each chunk of rows becomes a compact matrix of the features the
   // trees split on (src/device/csr_kernels.hip) that the forest kernels walk.  Narrower and wider
   // matrices (predict_disable_shape_check) need nothing more: missing features read 0 and
@@ -554,39 +564,14 @@ class Booster {
   bool PredictCSROnDevice(const void* indptr, int indptr_type, const int32_t* indices, const void* data,
                           int data_type, int64_t nindptr, int64_t nelem, int64_t ncol, int predict_type,
                           int start_iteration, int num_iteration, const Config& cfg, double* out, int64_t* out_len) {
-    DevicePredictKind kind;
     if (indptr_type != C_API_DTYPE_INT32 && indptr_type != C_API_DTYPE_INT64) return false;
-    if (!DevicePredictGate(data_type, nindptr - 1, ncol, predict_type, cfg, &kind)) return false;
-    std::unique_lock<std::shared_mutex> l(mu_);
-    if (!boosting_->PredictCSROnDevice(indptr, indptr_type == C_API_DTYPE_INT64, indices, data,
-                                       data_type == C_API_DTYPE_FLOAT64, nindptr, nelem, start_iteration, num_iteration,
-                                       kind, out)) {
-      return false;
-    }
-    *out_len = (nindptr - 1) * boosting_->NumPredictOneRow(start_iteration, num_iteration,
-                                                           kind == DevicePredictKind::Leaf,
-                                                           kind == DevicePredictKind::Contrib);
-    return true;
-  }
-
-  // ... and CSR arrays in device memory, into device memory (ops.forest_predict on a sparse tensor)
-  void PredictCSRDeviceBuffers(const void* d_indptr, int indptr_type, const int32_t* d_indices, const void* d_data,
-                               int data_type, int64_t nrow, int64_t nelem, int predict_type, int start_iteration,
-                               int num_iteration, double* d_out, int64_t out_len) {
-    DevicePredictKind kind;
-    if (!DeviceKindOf(predict_type, &kind) || kind == DevicePredictKind::Normal) {
-      Log::Fatal("forest prediction on device buffers: predict type %d is not raw, leaf or contrib", predict_type);
-    }
-    if (data_type != C_API_DTYPE_FLOAT32 && data_type != C_API_DTYPE_FLOAT64) {
-      Log::Fatal("forest prediction on device buffers: data must be float32 or float64");
-    }
-    if (indptr_type != C_API_DTYPE_INT32 && indptr_type != C_API_DTYPE_INT64) {
-      Log::Fatal("forest prediction on device buffers: indptr must be int32 or int64");
-    }
-    std::unique_lock<std::shared_mutex> l(mu_);
-    boosting_->PredictCSRDeviceBuffers(d_indptr, indptr_type == C_API_DTYPE_INT64, d_indices, d_data,
-                                       data_type == C_API_DTYPE_FLOAT64, nrow, nelem, start_iteration, num_iteration,
-                                       kind, d_out, out_len);
+    auto call = [&](DevicePredictKind kind) {
+      return boosting_->PredictCSROnDevice(indptr, indptr_type == C_API_DTYPE_INT64, indices, data,
+                                           data_type == C_API_DTYPE_FLOAT64, nindptr, nelem, start_iteration,
+                                           num_iteration, kind, out);
+    };
+    return PredictOnDevice(data_type, nindptr - 1, ncol, predict_type, start_iteration, num_iteration, cfg, out_len,
+                           call);
   }
 
   void CsrToSlots(const void* indptr, int indptr_type, const int32_t* indices, const void* data, int data_type,
@@ -605,38 +590,14 @@ class Booster {
   bool PredictCSCOnDevice(const void* col_ptr, int col_ptr_type, const int32_t* indices, const void* data,
                           int data_type, int64_t ncol_ptr, int64_t nelem, int64_t num_row, int predict_type,
                           int start_iteration, int num_iteration, const Config& cfg, double* out, int64_t* out_len) {
-    DevicePredictKind kind;
     if (col_ptr_type != C_API_DTYPE_INT32 && col_ptr_type != C_API_DTYPE_INT64) return false;
-    if (!DevicePredictGate(data_type, num_row, ncol_ptr - 1, predict_type, cfg, &kind)) return false;
-    std::unique_lock<std::shared_mutex> l(mu_);
-    if (!boosting_->PredictCSCOnDevice(col_ptr, col_ptr_type == C_API_DTYPE_INT64, indices, data,
-                                       data_type == C_API_DTYPE_FLOAT64, ncol_ptr, nelem, num_row, start_iteration,
-                                       num_iteration, kind, out)) {
-      return false;
-    }
-    *out_len = num_row * boosting_->NumPredictOneRow(start_iteration, num_iteration, kind == DevicePredictKind::Leaf,
-                                                     kind == DevicePredictKind::Contrib);
-    return true;
-  }
-
-  // ... and CSC arrays in device memory, into device memory (ops.forest_predict on a sparse_csc tensor)
-  void PredictCSCDeviceBuffers(const void* d_col_ptr, int col_ptr_type, const int32_t* d_indices, const void* d_data,
-                               int data_type, int64_t ncol, int64_t nelem, int64_t nrow, int predict_type,
-                               int start_iteration, int num_iteration, double* d_out, int64_t out_len) {
-    DevicePredictKind kind;
-    if (!DeviceKindOf(predict_type, &kind) || kind == DevicePredictKind::Normal) {
-      Log::Fatal("forest prediction on device buffers: predict type %d is not raw, leaf or contrib", predict_type);
-    }
-    if (data_type != C_API_DTYPE_FLOAT32 && data_type != C_API_DTYPE_FLOAT64) {
-      Log::Fatal("forest prediction on device buffers: data must be float32 or float64");
-    }
-    if (col_ptr_type != C_API_DTYPE_INT32 && col_ptr_type != C_API_DTYPE_INT64) {
-      Log::Fatal("forest prediction on device buffers: col_ptr must be int32 or int64");
-    }
-    std::unique_lock<std::shared_mutex> l(mu_);
-    boosting_->PredictCSCDeviceBuffers(d_col_ptr, col_ptr_type == C_API_DTYPE_INT64, d_indices, d_data,
-                                       data_type == C_API_DTYPE_FLOAT64, ncol, nelem, nrow, start_iteration,
-                                       num_iteration, kind, d_out, out_len);
+    auto call = [&](DevicePredictKind kind) {
+      return boosting_->PredictCSCOnDevice(col_ptr, col_ptr_type == C_API_DTYPE_INT64, indices, data,
+                                           data_type == C_API_DTYPE_FLOAT64, ncol_ptr, nelem, num_row, start_iteration,
+                                           num_iteration, kind, out);
+    };
+    return PredictOnDevice(data_type, num_row, ncol_ptr - 1, predict_type, start_iteration, num_iteration, cfg, out_len,
+                           call);
   }
 
   void CscToSlots(const void* col_ptr, int col_ptr_type, const int32_t* indices, const void* data, int data_type,
@@ -652,22 +613,6 @@ class Booster {
     boosting_->CscToSlotsOnHost(col_ptr, col_ptr_type == C_API_DTYPE_INT64, indices, data,
                                 data_type == C_API_DTYPE_FLOAT64, ncol_ptr, nelem, row0, rows, start_iteration,
                                 num_iteration, num_used, used, matrix);
-  }
-
-  // raw scores, leaf indices or contributions of a row-major matrix in device memory, into
-  // device memory (lightgbmv1_amd.ops.forest_predict): no row gate, no host round trip
-  void PredictDeviceBuffers(const void* d_data, int data_type, int64_t nrow, int32_t ncol, int predict_type,
-                            int start_iteration, int num_iteration, double* d_out, int64_t out_len) {
-    DevicePredictKind kind;
-    if (!DeviceKindOf(predict_type, &kind) || kind == DevicePredictKind::Normal) {
-      Log::Fatal("forest prediction on device buffers: predict type %d is not raw, leaf or contrib", predict_type);
-    }
-    if (data_type != C_API_DTYPE_FLOAT32 && data_type != C_API_DTYPE_FLOAT64) {
-      Log::Fatal("forest prediction on device buffers: data must be float32 or float64");
-    }
-    std::unique_lock<std::shared_mutex> l(mu_);
-    boosting_->PredictDeviceBuffers(d_data, data_type == C_API_DTYPE_FLOAT64, nrow, ncol, start_iteration,
-                                    num_iteration, kind, d_out, out_len);
   }
 
   void ContribFromPathTables(const double* data, int32_t nrow, int32_t ncol, int start_iteration, int num_iteration,
@@ -686,6 +631,23 @@ class Booster {
       case C_API_PREDICT_LEAF_INDEX: *kind = DevicePredictKind::Leaf; return true;
       case C_API_PREDICT_CONTRIB: *kind = DevicePredictKind::Contrib; return true;
       default: return false;
+    }
+  }
+
+  // what a prediction on device buffers computes, of float32 / float64 data
+  static DevicePredictKind DeviceBufferKind(int predict_type, int data_type) {
+    DevicePredictKind kind;
+    if (!DeviceKindOf(predict_type, &kind) || kind == DevicePredictKind::Normal) {
+      Log::Fatal("forest prediction on device buffers: predict type %d is not raw, leaf or contrib", predict_type);
+    }
+    if (data_type != C_API_DTYPE_FLOAT32 && data_type != C_API_DTYPE_FLOAT64) {
+      Log::Fatal("forest prediction on device buffers: data must be float32 or float64");
+    }
+    return kind;
+  }
+  static void CheckDevicePointerType(int type, const char* name) {
+    if (type != C_API_DTYPE_INT32 && type != C_API_DTYPE_INT64) {
+      Log::Fatal("forest prediction on device buffers: %s must be int32 or int64", name);
     }
   }
 
@@ -1837,6 +1799,22 @@ int LGBM_AMD_CscLaunchInfo(int64_t* out) {
   API_END();
 }
 
+int LGBM_AMD_PredictChunkPlan(int64_t nrow, int64_t budget, int64_t fixed, int64_t per_row, int64_t per_entry,
+                              int64_t forced, const int64_t* ptr, int64_t* out) {
+  API_BEGIN();
+  if (nrow < 1 || budget < 0 || fixed < 0 || per_row < 1 || per_entry < 0) {
+    Log::Fatal("PredictChunkPlan: need nrow >= 1, per_row >= 1 and no negative byte count");
+  }
+  const PredictChunkPlan plan =
+      PlanPredictChunks(nrow, budget, fixed, per_row, per_entry, forced, dev::kShapLanes, [&](int64_t rows) {
+        return ptr == nullptr ? int64_t{0} : MostChunkEntries(ptr, nrow, rows);
+      });
+  out[0] = plan.chunk;
+  out[1] = plan.entries;
+  out[2] = plan.fits ? 1 : 0;
+  API_END();
+}
+
 int LGBM_AMD_RefitLeafSums(const int32_t* leaf, const float* grad, const float* hess, int64_t n, int32_t num_leaves,
                            double* out_sums, int64_t* out_counts, int32_t* out_scale_exp) {
   API_BEGIN();
@@ -1952,30 +1930,39 @@ int LGBM_AMD_ConvertScores(int kind, double param, int num_class, int64_t n, con
 }
 
 namespace lgbm_amd {
-// (src/capi/ops_api.cpp: LGBMAMD_OpForestPredict; throws what the op reports)
+// raw scores, leaf indices or contributions of a row-major matrix in device memory, into device
+// memory (booster_device_buffers.h; lightgbmv1_amd.ops.forest_predict): no row gate, no host round trip
 void BoosterPredictDeviceBuffers(BoosterHandle handle, const void* d_data, int data_type, int64_t nrow, int32_t ncol,
                                  int predict_type, int start_iteration, int num_iteration, double* d_out,
                                  int64_t out_len) {
-  static_cast<Booster*>(handle)->PredictDeviceBuffers(d_data, data_type, nrow, ncol, predict_type, start_iteration,
-                                                      num_iteration, d_out, out_len);
+  const DevicePredictKind kind = Booster::DeviceBufferKind(predict_type, data_type);
+  const auto booster_lock = WriteLock(handle);
+  static_cast<Booster*>(handle)->boosting()->PredictDeviceBuffers(
+      d_data, data_type == C_API_DTYPE_FLOAT64, nrow, ncol, start_iteration, num_iteration, kind, d_out, out_len);
 }
-// (LGBMAMD_OpForestPredictCSR)
+// ... of CSR arrays in device memory (a sparse_csr tensor)
 void BoosterPredictCSRDeviceBuffers(BoosterHandle handle, const void* d_indptr, int indptr_type,
                                     const int32_t* d_indices, const void* d_data, int data_type, int64_t nrow,
                                     int64_t nelem, int predict_type, int start_iteration, int num_iteration,
                                     double* d_out, int64_t out_len) {
-  static_cast<Booster*>(handle)->PredictCSRDeviceBuffers(d_indptr, indptr_type, d_indices, d_data, data_type, nrow,
-                                                         nelem, predict_type, start_iteration, num_iteration, d_out,
-                                                         out_len);
+  const DevicePredictKind kind = Booster::DeviceBufferKind(predict_type, data_type);
+  Booster::CheckDevicePointerType(indptr_type, "indptr");
+  const auto booster_lock = WriteLock(handle);
+  static_cast<Booster*>(handle)->boosting()->PredictCSRDeviceBuffers(
+      d_indptr, indptr_type == C_API_DTYPE_INT64, d_indices, d_data, data_type == C_API_DTYPE_FLOAT64, nrow, nelem,
+      start_iteration, num_iteration, kind, d_out, out_len);
 }
-// (LGBMAMD_OpForestPredictCSC)
+// ... and of CSC arrays in device memory (a sparse_csc tensor)
 void BoosterPredictCSCDeviceBuffers(BoosterHandle handle, const void* d_col_ptr, int col_ptr_type,
                                     const int32_t* d_indices, const void* d_data, int data_type, int64_t ncol,
                                     int64_t nelem, int64_t nrow, int predict_type, int start_iteration,
                                     int num_iteration, double* d_out, int64_t out_len) {
-  static_cast<Booster*>(handle)->PredictCSCDeviceBuffers(d_col_ptr, col_ptr_type, d_indices, d_data, data_type, ncol,
-                                                         nelem, nrow, predict_type, start_iteration, num_iteration,
-                                                         d_out, out_len);
+  const DevicePredictKind kind = Booster::DeviceBufferKind(predict_type, data_type);
+  Booster::CheckDevicePointerType(col_ptr_type, "col_ptr");
+  const auto booster_lock = WriteLock(handle);
+  static_cast<Booster*>(handle)->boosting()->PredictCSCDeviceBuffers(
+      d_col_ptr, col_ptr_type == C_API_DTYPE_INT64, d_indices, d_data, data_type == C_API_DTYPE_FLOAT64, ncol, nelem, nrow,
+      start_iteration, num_iteration, kind, d_out, out_len);
 }
 }  // namespace lgbm_amd
 

@@ -27,6 +27,7 @@
 #include "../device/kernels.h"
 #include "../device/rank_tables.h"
 #include "../device/refit_quant.h"
+#include "booster_device_buffers.h"
 #include "lgbm_amd/c_api.h"
 #include "lgbm_amd/config.h"
 #include "lgbm_amd/dataset.h"
@@ -37,21 +38,6 @@
 #include "lgbm_amd/objective.h"
 
 using namespace lgbm_amd;
-
-namespace lgbm_amd {
-// src/capi/c_api.cpp (the Booster behind a handle lives there)
-void BoosterPredictDeviceBuffers(BoosterHandle handle, const void* d_data, int data_type, int64_t nrow, int32_t ncol,
-                                 int predict_type, int start_iteration, int num_iteration, double* d_out,
-                                 int64_t out_len);
-void BoosterPredictCSRDeviceBuffers(BoosterHandle handle, const void* d_indptr, int indptr_type,
-                                    const int32_t* d_indices, const void* d_data, int data_type, int64_t nrow,
-                                    int64_t nelem, int predict_type, int start_iteration, int num_iteration,
-                                    double* d_out, int64_t out_len);
-void BoosterPredictCSCDeviceBuffers(BoosterHandle handle, const void* d_col_ptr, int col_ptr_type,
-                                    const int32_t* d_indices, const void* d_data, int data_type, int64_t ncol,
-                                    int64_t nelem, int64_t nrow, int predict_type, int start_iteration,
-                                    int num_iteration, double* d_out, int64_t out_len);
-}  // namespace lgbm_amd
 
 namespace {
 

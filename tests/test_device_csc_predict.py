@@ -5,7 +5,8 @@ path: through Booster.predict / LGBM_BoosterPredictForCSC / LGBM_BoosterPredictS
 gate, row chunks, shape check) and through lightgbmv1_amd.ops.forest_predict on torch.sparse_csc
 GPU tensors.  Raw scores and leaf indices must be equal; contributions are held to the tolerance
 of tests/helpers/contrib_cases.py and are bit-equal to the device CSR path's (same compact matrix,
-same kernel).  What a matrix with repeated cells means comes from csc_meaning
+same kernel); in forced chunks the four host layouts (row-major, column-major, CSR, CSC) give the
+same doubles for every kind.  What a matrix with repeated cells means comes from csc_meaning
 (tests/helpers/csc_cases.py), never from toarray(), which sums them.
 LGBM_AMD_DevicePredictCount is asserted on every call, so a silent host fallback fails.
 """
@@ -196,10 +197,59 @@ def test_wide_sparse_matrix_in_chunks(wide, monkeypatch):
     assert np.array_equal(want["pred_leaf"], _device(bst, dense, pred_leaf=True))
 
 
-def test_chunked_rows_are_bit_equal(monkeypatch):
+def _three_chunks():
     c = cc.case("multiclass3")
     X = np.concatenate([c.X, c.X[::-1]])  # 3000 rows: two chunks of 1024 and one of 952
     X[[1023, 1024, 2047, 2999]] = 0.0     # all-zero rows on the chunk boundaries
+    return c, X
+
+
+def _for_mat(booster, X, kind):
+    """doubles from LGBM_BoosterPredictForMat on X in the layout it has (row- or column-major)"""
+    row_major = X.flags["C_CONTIGUOUS"]
+    assert X.dtype == np.float64 and (row_major or X.flags["F_CONTIGUOUS"])
+    width = ctypes.c_int64(0)
+    nat.call("LGBM_BoosterCalcNumPredict", booster.handle, nat.c_int(1), nat.c_int(kind), nat.c_int(0), nat.c_int(-1),
+             ctypes.byref(width))
+    out = np.empty((X.shape[0], width.value))
+    got = ctypes.c_int64(0)
+    nat.call("LGBM_BoosterPredictForMat", booster.handle, X.ctypes.data_as(ctypes.c_void_p), nat.c_int(nat.DTYPE_FLOAT64),
+             ctypes.c_int32(X.shape[0]), ctypes.c_int32(X.shape[1]), nat.c_int(1 if row_major else 0), nat.c_int(kind),
+             nat.c_int(0), nat.c_int(-1), nat.cstr("device_type=gpu"), ctypes.byref(got),
+             out.ctypes.data_as(ctypes.POINTER(ctypes.c_double)))
+    assert got.value == out.size
+    return out
+
+
+@pytest.mark.parametrize("kind", [nat.PREDICT_RAW_SCORE, nat.PREDICT_NORMAL, nat.PREDICT_LEAF_INDEX, nat.PREDICT_CONTRIB],
+                         ids=["raw", "normal", "leaf", "contrib"])
+def test_the_four_layouts_agree_in_chunks(kind, monkeypatch):
+    """one loop stages, runs and copies back the chunks of every layout: 3000 rows in chunks of
+    1024 give the same doubles as row-major, column-major, CSR and CSC input, one device call each,
+    and (but for contributions, which the host computes by another algorithm) the host's"""
+    c, X = _three_chunks()
+    m = sp.csc_matrix(X)
+    monkeypatch.setenv("LGBM_AMD_PREDICT_CHUNK_ROWS", "1024")
+    got = {}
+    for layout, predict in [("row-major", lambda: _for_mat(c.booster, X, kind)),
+                            ("column-major", lambda: _for_mat(c.booster, np.asfortranarray(X), kind)),
+                            ("csr", lambda: _capi(c.booster, m.tocsr(), kind)),
+                            ("csc", lambda: _capi(c.booster, m, kind))]:
+        before = _device_calls()
+        got[layout] = predict()
+        assert _device_calls() == before + 1, "%s did not take one device call" % layout
+    for layout, out in got.items():
+        assert out.shape == got["row-major"].shape and np.array_equal(out, got["row-major"]), layout
+    if kind != nat.PREDICT_CONTRIB:
+        monkeypatch.setenv("LGBM_AMD_HOST_PREDICT", "1")
+        before = _device_calls()
+        host = _for_mat(c.booster, X, kind)
+        assert _device_calls() == before
+        assert np.array_equal(got["row-major"], host)
+
+
+def test_chunked_rows_are_bit_equal(monkeypatch):
+    c, X = _three_chunks()
     m = sp.csc_matrix(X)
     assert not np.isin(m.indices, [1023, 1024, 2047, 2999]).any()
     for kw in KINDS:
