@@ -38,6 +38,10 @@ $(BUILD)/%.hip.o: src/%.hip $(HEADERS)
 	@mkdir -p $(dir $@)
 	$(HIPCC) $(HIPFLAGS) $(HIPEXTRA) -c $< -o $@
 
+# no packed-fp32 instructions in the binning of device matrices (its doubles and floats are
+# compared bit for bit with the host's)
+$(BUILD)/device/tensor_bin_kernels.hip.o: HIPEXTRA += -Xclang -target-feature -Xclang -packed-fp32-ops
+
 $(LIB): $(HOST_OBJS) $(DEV_OBJS)
 	@mkdir -p $(LIBDIR)
 	$(CXX) -o $@ $^ $(LDFLAGS)

@@ -23,6 +23,10 @@ typedef void* FastConfigHandle;
 #define C_API_DTYPE_FLOAT64 (1)
 #define C_API_DTYPE_INT32 (2)
 #define C_API_DTYPE_INT64 (3)
+// element types of a matrix in device memory (LGBM_AMD_DatasetCreateFromDeviceMat and
+// LGBM_AMD_TensorGroupBinsOnHost only)
+#define C_API_DTYPE_FLOAT16 (4)
+#define C_API_DTYPE_BFLOAT16 (5)
 
 #define C_API_PREDICT_NORMAL (0)
 #define C_API_PREDICT_RAW_SCORE (1)
@@ -325,6 +329,33 @@ LIGHTGBM_C_EXPORT int LGBM_AMD_CsrBinLaunchInfo(int64_t* out);
 // matrices this process has binned on the device: dense (LGBM_DatasetCreateFromMat) and CSR
 // (LGBM_DatasetCreateFromCSR); tests: whether a construction took the device path
 LIGHTGBM_C_EXPORT int LGBM_AMD_DeviceBinStats(int64_t* dense_calls, int64_t* csr_calls);
+// A dataset from a matrix in device memory, read where it lies (src/device/tensor_bin_kernels.hip):
+// nrow x ncol elements of data_type (C_API_DTYPE_FLOAT32 / FLOAT64 / FLOAT16 / BFLOAT16) on HIP
+// device device_id, element (r, c) at d_data[r * row_stride + c * col_stride] (strides in elements,
+// not negative).  The bin sample is gathered on the device and the mappers found on the host, or
+// taken from `reference`; the result is the dataset LGBM_DatasetCreateFromMat builds from a host
+// copy of the values as float64.  Runs on device_id's null stream (the caller has finished its own
+// writes of the matrix), restores the caller's device and returns after everything has finished
+LIGHTGBM_C_EXPORT int LGBM_AMD_DatasetCreateFromDeviceMat(const void* d_data, int data_type, int32_t nrow,
+                                                          int32_t ncol, int64_t row_stride, int64_t col_stride,
+                                                          int device_id, const char* parameters,
+                                                          const DatasetHandle reference, DatasetHandle* out);
+// the rule of that path (src/device/tensor_bins.h) evaluated on the host for a host matrix of the
+// same description, with a constructed dataset's bin mappers (no GPU): bins is row-major
+// [nrow][*num_groups], the layout of LGBM_AMD_DatasetGetGroupBins, with -1 in the columns of the
+// groups the device path hands to the host push (sparse storage, a categorical feature above the
+// kernel's table).  With bins or data null only *num_groups is returned
+LIGHTGBM_C_EXPORT int LGBM_AMD_TensorGroupBinsOnHost(DatasetHandle handle, const void* data, int data_type,
+                                                     int32_t nrow, int32_t ncol, int64_t row_stride,
+                                                     int64_t col_stride, int32_t* bins, int* num_groups);
+// the launch shape of that path: out[0] the rows of a binning workgroup, out[1] the edge of the
+// (sample, column) tile of the sample gather, out[2] the most categories of a feature binned on
+// the device, out[3] the bytes of a row in one batch of columns, out[4] the values of a tensor from
+// which the Python package takes this path without being told to (kTensorBinMinValues)
+LIGHTGBM_C_EXPORT int LGBM_AMD_TensorBinLaunchInfo(int64_t* out);
+// matrices this process has taken through LGBM_AMD_DatasetCreateFromDeviceMat; tests: whether a
+// construction took that path
+LIGHTGBM_C_EXPORT int LGBM_AMD_DeviceBinTensorStats(int64_t* tensor_calls);
 // the rule of the device binning of a CSC matrix (src/device/csc_bins.h) evaluated on the host
 // with a constructed dataset's bin mappers (no GPU): bins is row-major [num_row][*num_groups], the
 // layout of LGBM_AMD_CsrToGroupBins.  Entries on a row outside [0, num_row), on a column not below

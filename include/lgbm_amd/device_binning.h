@@ -1,5 +1,6 @@
 // Value -> bin mapping of dense, CSR and CSC matrices on the device (src/device/bin_kernels.hip,
-// src/device/csr_bin_kernels.hip, src/device/csc_bin_kernels.hip; reference
+// src/device/csr_bin_kernels.hip, src/device/csc_bin_kernels.hip) and of matrices already in
+// device memory (src/device/tensor_bin_kernels.hip); reference
 // include/LightGBM/bin.h:132 ValueToBin).
 #pragma once
 
@@ -100,6 +101,54 @@ void CscBinLaunchInfo(int64_t* out);
 // (LGBM_DatasetCreateFromCSC), in this process
 void DeviceBinCscStats(int64_t* csc_calls, int64_t* column_samples);
 void NoteCscColumnSample();
+
+// A matrix that already lies in device memory (src/device/tensor_bin_kernels.hip): nrow x ncol
+// elements of data_type (C_API_DTYPE_FLOAT32 / FLOAT64 / FLOAT16 / BFLOAT16) on device_id, element
+// (r, c) at data[r * row_stride + c * col_stride] (strides in elements: row-major, column-major
+// and sliced views alike).  Both calls below run on device_id's null stream, restore the caller's
+// device and return after everything has finished.
+struct DeviceTensor {
+  const void* data;
+  int data_type;
+  int32_t nrow, ncol;
+  int64_t row_stride, col_stride;
+  int device_id;
+};
+
+// The bin sample of the matrix: rows `rows` (SampleRows) gathered on the device, copied back and
+// filtered by the zero / NaN rule of the host's row reader into sv / si [ncol], the arguments of
+// Dataset::ConstructFromSample -- the same values at the same sample positions as from a host copy
+void SampleDeviceTensor(const DeviceTensor& t, const std::vector<int>& rows, std::vector<std::vector<double>>* sv,
+                        std::vector<std::vector<int>>* si);
+
+// Writes every group of `ds` (its mappers found, or taken from a reference) from the matrix,
+// bit-identical to the column loop of LGBM_DatasetCreateFromMat on a host copy: dense groups of
+// numerical and categorical members by k_tensor_to_group_bins; the columns of the other groups
+// (sparse storage, a categorical feature of more than kTensorMaxCategories categories) gathered as
+// doubles and pushed through Dataset::PushColumnValue.  The caller calls FinishLoad.
+void BinDeviceTensor(Dataset* ds, const DeviceTensor& t);
+
+// The rule of src/device/tensor_bins.h on the host, for a host matrix of the same description, with
+// the dataset's mappers: bins[nrow][ds.num_groups()], -1 in the columns of the groups that
+// BinDeviceTensor hands to the host.  No GPU.
+void EvalTensorGroupBins(const Dataset& ds, const void* data, int data_type, int32_t nrow, int32_t ncol,
+                         int64_t row_stride, int64_t col_stride, int32_t* bins);
+
+// A GPU tensor of fewer values goes through the host copy it went through before, unless it is
+// bfloat16 (which has no host path) or LGBM_AMD_DEVICE_BINNING=1: 10K x 28 was the smallest size
+// timed at which reading the tensor in place was ahead of the host copy (3.2 ms against 4.8 ms for the
+// training set, 0.58 ms against 1.07 ms for a reference= set); at 1K x 28 it was behind by 0.35 ms
+// and 0.4 ms, more than twice the run-to-run spread (profiles/r19_tensor_dataset.md).  The Python
+// dispatch reads it from TensorBinLaunchInfo.
+constexpr int64_t kTensorBinMinValues = 280000;
+
+// out[0]: rows of a k_tensor_to_group_bins workgroup; out[1]: the (sample, column) tile edge of
+// k_gather_sample; out[2]: kTensorMaxCategories; out[3]: bytes of a row in one value batch; out[4]:
+// kTensorBinMinValues
+void TensorBinLaunchInfo(int64_t* out);
+
+// matrices that went through BinDeviceTensor in this process
+void DeviceBinTensorStats(int64_t* tensor_calls);
 
 // how many matrices went through DeviceBinDenseMatrix / DeviceBinCsrMatrix in this process
 void DeviceBinStats(int64_t* dense_calls, int64_t* csr_calls);

@@ -19,6 +19,7 @@ class LightGBMError(Exception):
 
 # C API enum values (c_api.h)
 DTYPE_FLOAT32, DTYPE_FLOAT64, DTYPE_INT32, DTYPE_INT64 = 0, 1, 2, 3
+DTYPE_FLOAT16, DTYPE_BFLOAT16 = 4, 5  # (matrices in device memory only)
 PREDICT_NORMAL, PREDICT_RAW_SCORE, PREDICT_LEAF_INDEX, PREDICT_CONTRIB = 0, 1, 2, 3
 MATRIX_CSR, MATRIX_CSC = 0, 1
 IMPORTANCE_TYPES = {"split": 0, "gain": 1}

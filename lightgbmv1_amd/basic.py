@@ -148,8 +148,43 @@ def _build_from_sparse(m, params_str, ref):
     return out
 
 
+# torch dtype of a GPU tensor that LGBM_AMD_DatasetCreateFromDeviceMat reads in place -> C API code
+_DEVICE_MAT_CODES = {"torch.float32": nat.DTYPE_FLOAT32, "torch.float64": nat.DTYPE_FLOAT64,
+                     "torch.float16": nat.DTYPE_FLOAT16, "torch.bfloat16": nat.DTYPE_BFLOAT16}
+
+
+def _is_device_matrix(data):
+    """A non-empty 2-D floating torch tensor on a GPU that is binned where it lies, whatever its
+    strides (src/device/tensor_bin_kernels.hip): never with LGBM_AMD_DEVICE_BINNING=0; otherwise
+    from kTensorBinMinValues values on, and at every size with =1 or as bfloat16 (no host path)."""
+    if not (_is_gpu_tensor(data) and data.dim() == 2 and str(data.dtype) in _DEVICE_MAT_CODES and data.numel() > 0):
+        return False
+    knob = os.environ.get("LGBM_AMD_DEVICE_BINNING", "")
+    if knob.startswith("0"):
+        return False
+    if knob.startswith("1") or str(data.dtype) == "torch.bfloat16":
+        return True
+    info = (ctypes.c_int64 * 5)()
+    nat.call("LGBM_AMD_TensorBinLaunchInfo", info)
+    return data.numel() >= info[4]
+
+
+def _build_from_device(data, params_str, ref):
+    import torch
+    t = data.detach()
+    torch.cuda.synchronize(t.device)  # (the caller's writes of the tensor; the library uses the null stream)
+    out = ctypes.c_void_p()
+    nat.call("LGBM_AMD_DatasetCreateFromDeviceMat", ctypes.c_void_p(t.data_ptr()),
+             nat.c_int(_DEVICE_MAT_CODES[str(t.dtype)]), ctypes.c_int32(t.shape[0]), ctypes.c_int32(t.shape[1]),
+             ctypes.c_int64(t.stride(0)), ctypes.c_int64(t.stride(1)), nat.c_int(t.device.index),
+             nat.cstr(params_str), ref, ctypes.byref(out))
+    return out
+
+
 def _input_kind(data):
     """Which builder / predictor handles `data` (None: try converting to CSR)."""
+    if _is_device_matrix(data):
+        return "device"
     if isinstance(data, string_type):
         return "file"
     if scipy.sparse.isspmatrix_csr(data):
@@ -173,6 +208,7 @@ _BUILDERS = {
     "blocks": _build_from_blocks,
     "csr": _build_from_sparse,
     "csc": _build_from_sparse,
+    "device": _build_from_device,
     "datatable": lambda d, p, r: _build_from_dense(d.to_numpy(), p, r),
 }
 
@@ -250,7 +286,9 @@ class Dataset:
         if data is None:
             self.handle = None
             return self
-        data, label, weight, init_score = (inp.to_host(x) for x in (data, label, weight, init_score))
+        label, weight, init_score = (inp.to_host(x) for x in (label, weight, init_score))
+        if not _is_device_matrix(data):  # (a GPU matrix is read where it lies)
+            data = inp.to_host(data)
         if reference is not None:
             self.pandas_categorical = reference.pandas_categorical
             categorical_feature = reference.categorical_feature

@@ -323,6 +323,26 @@ def csr_group_bins(dataset, X):
     return out
 
 
+def tensor_bin_launch_info():
+    """The launch shape of the binning of a GPU tensor handed to ``lgb.Dataset``
+    (src/device/tensor_bin_kernels.hip): ``tile_rows`` (rows of a binning workgroup), ``gather_tile``
+    (sampled rows and columns of a workgroup of the sample gather), ``max_categories`` (a categorical
+    feature with more categories is pushed on the host), ``batch_row_bytes`` (bytes of a row that
+    one batch of columns holds) and ``min_values`` (smaller tensors take the host copy unless they
+    are bfloat16 or ``LGBM_AMD_DEVICE_BINNING=1``)."""
+    out = (ctypes.c_int64 * 5)()
+    _native_call("LGBM_AMD_TensorBinLaunchInfo", out)
+    return {"tile_rows": out[0], "gather_tile": out[1], "max_categories": out[2], "batch_row_bytes": out[3],
+            "min_values": out[4]}
+
+
+def tensor_bin_stats():
+    """How many GPU tensors this process has binned where they lay (LGBM_AMD_DatasetCreateFromDeviceMat)."""
+    n = ctypes.c_int64(-1)
+    _native_call("LGBM_AMD_DeviceBinTensorStats", ctypes.byref(n))
+    return n.value
+
+
 def csc_bin_launch_info():
     """The launch shape of the CSC binning kernels (src/device/csc_bin_kernels.hip):
     ``segment_entries`` (the stored entries of a column that one wave takes),
