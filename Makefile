@@ -41,6 +41,9 @@ $(BUILD)/%.hip.o: src/%.hip $(HEADERS)
 # no packed-fp32 instructions in the binning of device matrices (its doubles and floats are
 # compared bit for bit with the host's)
 $(BUILD)/device/tensor_bin_kernels.hip.o: HIPEXTRA += -Xclang -target-feature -Xclang -packed-fp32-ops
+# (the sort moves the bits of doubles and computes nothing in floating point: the flag only keeps
+# the rule that new device code is built without those instructions)
+$(BUILD)/device/bin_find_kernels.hip.o: HIPEXTRA += -Xclang -target-feature -Xclang -packed-fp32-ops
 
 $(LIB): $(HOST_OBJS) $(DEV_OBJS)
 	@mkdir -p $(LIBDIR)

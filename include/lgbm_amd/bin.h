@@ -15,6 +15,17 @@
 
 namespace lgbm_amd {
 
+// BinMapper::SampleDistinct of every column of a sample, found elsewhere (on the device, or by the
+// host evaluator of the device's rule): column c's runs are [begin[c], begin[c + 1]) of distinct /
+// counts; num_values[c] values went into them and nan_cnt[c] NaNs stood beside them
+struct SampleDistinctLists {
+  std::vector<int64_t> begin{0};
+  std::vector<double> distinct;
+  std::vector<int32_t> counts;
+  std::vector<int32_t> num_values, nan_cnt;
+  std::vector<int32_t> sort_passes;  // device only: radix passes each column's sort ran (of 8)
+};
+
 class BinMapper {
  public:
   BinMapper();
@@ -22,6 +33,19 @@ class BinMapper {
   void FindBin(double* values, int num_values, size_t total_sample_cnt, int max_bin, int min_data_in_bin,
                int min_split_data, bool pre_filter, BinType bin_type, bool use_missing, bool zero_as_missing,
                const std::vector<double>& forced_upper_bounds);
+  // FindBin's two halves.  SampleDistinct: the rule of one column of the sample (zeros already
+  // dropped by the caller): NaNs dropped and counted into *nan_cnt, the rest sorted ascending in
+  // place, a new run opened where !CheckDoubleEqualOrdered(v[i - 1], v[i]), a run's value its last
+  // element; returns the values kept.  The device computes the same lists for a GPU tensor
+  // (src/device/sample_distinct.h, src/device/bin_find_kernels.hip).
+  static int SampleDistinct(double* values, int num_values, std::vector<double>* distinct, std::vector<int>* counts,
+                            int* nan_cnt);
+  // ... and everything after it: the zero entry put in its place among the num_distinct runs (of
+  // num_values values; nan_cnt NaNs beside them), then the boundary search
+  void FindBinFromDistinct(const double* sample_distinct, const int* sample_counts, int num_distinct, int num_values,
+                           int nan_cnt, size_t total_sample_cnt, int max_bin, int min_data_in_bin,
+                           int min_split_data, bool pre_filter, BinType bin_type, bool use_missing,
+                           bool zero_as_missing, const std::vector<double>& forced_upper_bounds);
 
   uint32_t ValueToBin(double value) const;
   double BinToValue(uint32_t bin) const {

@@ -353,9 +353,33 @@ LIGHTGBM_C_EXPORT int LGBM_AMD_TensorGroupBinsOnHost(DatasetHandle handle, const
 // the device, out[3] the bytes of a row in one batch of columns, out[4] the values of a tensor from
 // which the Python package takes this path without being told to (kTensorBinMinValues)
 LIGHTGBM_C_EXPORT int LGBM_AMD_TensorBinLaunchInfo(int64_t* out);
-// matrices this process has taken through LGBM_AMD_DatasetCreateFromDeviceMat; tests: whether a
-// construction took that path
-LIGHTGBM_C_EXPORT int LGBM_AMD_DeviceBinTensorStats(int64_t* tensor_calls);
+// matrices this process has taken through LGBM_AMD_DatasetCreateFromDeviceMat, and bin samples
+// whose distinct values the device found (below); tests: whether a construction took those paths.
+// Either pointer may be null
+LIGHTGBM_C_EXPORT int LGBM_AMD_DeviceBinTensorStats(int64_t* tensor_calls, int64_t* bin_find_calls);
+// The first step of the bin finder (BinMapper::FindBin: the sort of a column's sample and its
+// distinct values) as the device computes it for the sample of a GPU tensor
+// (src/device/bin_find_kernels.hip, the rule in src/device/sample_distinct.h), evaluated on the
+// host (no GPU): sample is column-major [ncol][ns].  Column c's runs are
+// [begin[c], begin[c + 1]) of distinct / counts (each with room for ns * ncol entries; begin:
+// ncol + 1), ascending, zeros (|v| <= 1e-35f) and NaNs left out; nan_cnt[c] counts its NaNs
+LIGHTGBM_C_EXPORT int LGBM_AMD_SampleDistinct(const double* sample, int64_t ns, int32_t ncol, double* distinct,
+                                              int32_t* counts, int64_t* begin, int32_t* nan_cnt);
+// ... and by the kernels, for rows `rows` (num_rows of them; null: every row) of a matrix in device
+// memory, described as for LGBM_AMD_DatasetCreateFromDeviceMat: the gather and the kernels of that
+// call's sample.  distinct / counts have room for num_rows * ncol entries; sort_passes (ncol, or
+// null) receives how many of the eight radix passes each column's sort ran
+LIGHTGBM_C_EXPORT int LGBM_AMD_DeviceSampleDistinct(const void* d_data, int data_type, int32_t nrow, int32_t ncol,
+                                                    int64_t row_stride, int64_t col_stride, int device_id,
+                                                    const int32_t* rows, int32_t num_rows, double* distinct,
+                                                    int32_t* counts, int64_t* begin, int32_t* nan_cnt,
+                                                    int32_t* sort_passes);
+// the launch shape of those kernels: out[0] the keys of a scatter tile of the sort, out[1] the
+// threads of a workgroup (one per column), out[2] the entries per step of the compaction and of
+// the run pass, out[3] the sampled rows from which, and out[4] the sampled values (rows x columns)
+// up to which, a Dataset takes this path without being told to (kBinFindMinSampleRows,
+// kBinFindMaxSampleValues)
+LIGHTGBM_C_EXPORT int LGBM_AMD_BinFindLaunchInfo(int64_t* out);
 // the rule of the device binning of a CSC matrix (src/device/csc_bins.h) evaluated on the host
 // with a constructed dataset's bin mappers (no GPU): bins is row-major [num_row][*num_groups], the
 // layout of LGBM_AMD_CsrToGroupBins.  Entries on a row outside [0, num_row), on a column not below

@@ -137,11 +137,14 @@ class Dataset {
   // --- construction -------------------------------------------------------------
   // Build bin mappers from a column-wise sample of non-zero values (values may be NaN)
   // and allocate storage for `num_data` rows.  Mirrors DatasetLoader::ConstructFromSampleData.
+  // With `distinct` (the columns' BinMapper::SampleDistinct, found on the device) the mappers come
+  // from BinMapper::FindBinFromDistinct instead of FindBin: the same mappers without the sort.
   void ConstructFromSample(std::vector<std::vector<double>>* sample_values,
                            std::vector<std::vector<int>>* sample_indices, int num_col, size_t total_sample_cnt,
                            data_size_t num_data, const Config& cfg,
                            const std::unordered_set<int>& categorical, const std::unordered_set<int>& ignored,
-                           const std::vector<std::vector<double>>& forced_bins);
+                           const std::vector<std::vector<double>>& forced_bins,
+                           const SampleDistinctLists* distinct = nullptr);
   // Build from already-computed bin mappers (distributed exchange / binary load)
   void ConstructFromBinMappers(std::vector<std::unique_ptr<BinMapper>>* mappers, data_size_t num_data,
                                const Config& cfg, std::vector<std::vector<int>>* sample_indices,

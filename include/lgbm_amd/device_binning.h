@@ -12,6 +12,7 @@
 namespace lgbm_amd {
 
 class Dataset;
+struct SampleDistinctLists;  // (lgbm_amd/bin.h)
 
 // the HIP device a dataset under `cfg` is binned on (gpu_device_id, else LOCAL_RANK, else 0), or
 // -1: none visible
@@ -117,9 +118,40 @@ struct DeviceTensor {
 
 // The bin sample of the matrix: rows `rows` (SampleRows) gathered on the device, copied back and
 // filtered by the zero / NaN rule of the host's row reader into sv / si [ncol], the arguments of
-// Dataset::ConstructFromSample -- the same values at the same sample positions as from a host copy
+// Dataset::ConstructFromSample -- the same values at the same sample positions as from a host copy.
+// With `distinct`, every column's distinct values (BinMapper::SampleDistinct) are found on the
+// device as well (src/device/bin_find_kernels.hip): each pass of columns is sorted after its copy
+// to the host has been issued, while the host filters that copy, and only the runs come back.
 void SampleDeviceTensor(const DeviceTensor& t, const std::vector<int>& rows, std::vector<std::vector<double>>* sv,
-                        std::vector<std::vector<int>>* si);
+                        std::vector<std::vector<int>>* si, SampleDistinctLists* distinct = nullptr);
+
+// Whether the bin finder of a GPU tensor's sample (sample_cnt rows x ncol columns) takes its
+// distinct values from the device: LGBM_AMD_DEVICE_BIN_FIND=0 never, =1 always; otherwise for
+// samples of at least kBinFindMinSampleRows rows and at most kBinFindMaxSampleValues values.  Never
+// when loading is distributed (each rank finds the bins of its own block of columns from the host
+// sample).  Every size timed inside that window was ahead of the host sort by more than the
+// run-to-run spread (10K x 28: 2.5 against 3.0 ms; 200K x 28, the sample of 10M x 28: 169 against
+// 177 ms); shorter columns sort too quickly on the host to pay for the launches, and above the
+// window the runs of continuous columns -- as many as the sample has values, 12 bytes each -- cost
+// more to copy back than 16 host threads need to sort: 50K x 200 (10M values) was a tie, 100K x 200
+// behind by 5 %, 200K x 2000 by 30 % (profiles/r20_device_bin_finder.md).
+constexpr int64_t kBinFindMinSampleRows = 10000;
+constexpr int64_t kBinFindMaxSampleValues = 5600000;
+bool UseDeviceBinFind(int64_t sample_cnt, int64_t ncol);
+
+// the host evaluator of the kernels' rule (src/device/sample_distinct.h) on a column-major sample
+// [ncol][ns], or on columns of their own lengths (LGBM_AMD_DEVICE_BIN_FIND=2).  No GPU.
+void EvalSampleDistinctLists(const double* sample, int64_t ns, int32_t ncol, SampleDistinctLists* out);
+void EvalSampleDistinctLists(const std::vector<std::vector<double>>& columns, SampleDistinctLists* out);
+
+// out[0]: keys of a scatter tile of the sort; out[1]: threads of its workgroup (one per column);
+// out[2]: entries per step of the compaction and of the run pass; out[3]: kBinFindMinSampleRows;
+// out[4]: kBinFindMaxSampleValues
+void BinFindLaunchInfo(int64_t* out);
+
+// samples whose distinct values came from the device in this process
+void NoteDeviceBinFind();
+int64_t DeviceBinFindCalls();
 
 // Writes every group of `ds` (its mappers found, or taken from a reference) from the matrix,
 // bit-identical to the column loop of LGBM_DatasetCreateFromMat on a host copy: dense groups of
@@ -147,8 +179,9 @@ constexpr int64_t kTensorBinMinValues = 280000;
 // kTensorBinMinValues
 void TensorBinLaunchInfo(int64_t* out);
 
-// matrices that went through BinDeviceTensor in this process
-void DeviceBinTensorStats(int64_t* tensor_calls);
+// matrices that went through BinDeviceTensor in this process, and samples whose distinct values
+// the device found (either pointer may be null)
+void DeviceBinTensorStats(int64_t* tensor_calls, int64_t* bin_find_calls);
 
 // how many matrices went through DeviceBinDenseMatrix / DeviceBinCsrMatrix in this process
 void DeviceBinStats(int64_t* dense_calls, int64_t* csr_calls);

@@ -54,6 +54,7 @@ constexpr int kQueryMetricDeviceMaxDocs = 16384;
   X(HostRefit, "LGBM_AMD_HOST_REFIT", "1: a device booster refits with the CPU learner and a tree walk of the scores")  \
   X(HostSparse, "LGBM_AMD_HOST_SPARSE", "0/1: dense / sparse host storage of every group")                     \
   X(DeviceBinning, "LGBM_AMD_DEVICE_BINNING", "0/1: value-to-bin on the host / the GPU")                       \
+  X(DeviceBinFind, "LGBM_AMD_DEVICE_BIN_FIND", "0/1: the sort and distinct values of a GPU tensor's bin sample on the host / the GPU (auto by sample size); 2: by the host evaluator of the kernels' rule, host matrices too (tests)")  \
   X(NoGraph, "LGBM_AMD_NO_GRAPH", "1: kernels launched eagerly instead of from hipGraphs")                     \
   X(GraphCollectives, "LGBM_AMD_GRAPH_COLLECTIVES", "0: distributed split steps launched eagerly")             \
   X(StaticOwners, "LGBM_AMD_STATIC_OWNERS", "1: data-parallel keeps static feature owners")                    \

@@ -35,6 +35,10 @@ the kernels can be checked one by one against plain PyTorch references
   objective's output transform of raw scores (src/device/score_convert.h; reference
   ObjectiveFunction::ConvertOutput) and float16 / bfloat16 / float32 / float64 gradients as the
   learner's float32; :func:`custom_launch_info` gives their launch shape
+* :func:`sample_distinct` -- the distinct values and counts of every column of a bin sample of a
+  GPU tensor, the first step of the bin finder, by the kernels a training ``lgb.Dataset(gpu_tensor)``
+  runs (src/device/bin_find_kernels.hip; reference BinMapper::FindBin's sort and run-length pass);
+  :func:`bin_find_launch_info` gives their launch shape
 
 There is no host fallback: the ops need a GPU and the in-tree library.
 """
@@ -47,7 +51,7 @@ from ..basic import _load_lib
 
 __all__ = ["gradients", "metric", "sample_rows", "forest_predict", "leaf_sums", "add_leaf_values",
            "refit_launch_info", "csc_launch_info", "csr_group_bins", "csr_bin_launch_info",
-           "convert_scores", "cast_gradients", "custom_launch_info"]
+           "convert_scores", "cast_gradients", "custom_launch_info", "sample_distinct", "bin_find_launch_info"]
 
 
 def _torch():
@@ -336,11 +340,61 @@ def tensor_bin_launch_info():
             "min_values": out[4]}
 
 
-def tensor_bin_stats():
-    """How many GPU tensors this process has binned where they lay (LGBM_AMD_DatasetCreateFromDeviceMat)."""
-    n = ctypes.c_int64(-1)
-    _native_call("LGBM_AMD_DeviceBinTensorStats", ctypes.byref(n))
-    return n.value
+def tensor_bin_stats(bin_find=False):
+    """How many GPU tensors this process has binned where they lay (LGBM_AMD_DatasetCreateFromDeviceMat);
+    with ``bin_find``, how many bin samples had their distinct values found on the device instead
+    (src/device/bin_find_kernels.hip: training sets from a GPU tensor, and :func:`sample_distinct`)."""
+    n, m = ctypes.c_int64(-1), ctypes.c_int64(-1)
+    _native_call("LGBM_AMD_DeviceBinTensorStats", ctypes.byref(n), ctypes.byref(m))
+    return m.value if bin_find else n.value
+
+
+def bin_find_launch_info():
+    """The launch shape of the device bin finder's first step (src/device/bin_find_kernels.hip: one
+    workgroup per column of the bin sample): ``tile`` (keys of a scatter tile of the radix sort),
+    ``block`` (threads of the workgroup), ``size_thresholds`` (every other sample size at which the
+    kernel's loops turn over: the entries per step of the compaction and of the run pass), and the
+    gate of a training Dataset of a GPU tensor when ``LGBM_AMD_DEVICE_BIN_FIND`` is unset: at least
+    ``min_sample_rows`` sampled rows and at most ``max_sample_values`` sampled values (rows x columns)."""
+    out = (ctypes.c_int64 * 5)()
+    _native_call("LGBM_AMD_BinFindLaunchInfo", out)
+    return {"tile": out[0], "block": out[1], "size_thresholds": [out[2]], "min_sample_rows": out[3],
+            "max_sample_values": out[4]}
+
+
+def sample_distinct(X, rows=None, sort_passes=False):
+    """The first step of the bin finder on the sample ``X[rows]`` (all rows by default) of a 2-D
+    float16, bfloat16, float32 or float64 GPU tensor of any strides, by the gather and the kernels
+    that a training ``lgb.Dataset(X)`` runs: per column, zeros (``|v| <= 1e-35f``) and NaNs left
+    out, the rest sorted and collapsed into runs of values at most one ulp apart from their
+    neighbour.  Returns a list with ``(distinct, counts, na_cnt)`` per column: the runs' largest
+    values ascending (float64 array), their lengths (int32 array) and the column's NaN count.  With
+    ``sort_passes`` a fourth entry tells how many of the eight radix passes the column's sort ran
+    (the others had nothing to move: 5 at most for float32, 3 for float16 and bfloat16)."""
+    torch = _torch()
+    from ..basic import _DEVICE_MAT_CODES
+    if not isinstance(X, torch.Tensor) or X.device.type != "cuda" or X.dim() != 2 or X.numel() == 0 or \
+            str(X.dtype) not in _DEVICE_MAT_CODES:
+        raise LightGBMError("X must be a non-empty 2-d float16, bfloat16, float32 or float64 torch tensor on the GPU")
+    idx, idx_p, ns = _host_i32(rows, "rows")
+    if rows is None:
+        ns = X.shape[0]
+    ncol = X.shape[1]
+    distinct = np.empty(max(1, ns * ncol), dtype=np.float64)
+    counts = np.empty(max(1, ns * ncol), dtype=np.int32)
+    begin = np.zeros(ncol + 1, dtype=np.int64)
+    na, passes = np.zeros(ncol, dtype=np.int32), np.zeros(ncol, dtype=np.int32)
+    t = X.detach()
+    torch.cuda.synchronize(t.device)
+    _native_call("LGBM_AMD_DeviceSampleDistinct", ctypes.c_void_p(t.data_ptr()),
+                 ctypes.c_int(_DEVICE_MAT_CODES[str(t.dtype)]), ctypes.c_int32(t.shape[0]), ctypes.c_int32(ncol),
+                 ctypes.c_int64(t.stride(0)), ctypes.c_int64(t.stride(1)), ctypes.c_int(t.device.index), idx_p,
+                 ctypes.c_int32(ns), distinct.ctypes.data_as(ctypes.POINTER(ctypes.c_double)),
+                 counts.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)),
+                 begin.ctypes.data_as(ctypes.POINTER(ctypes.c_int64)), na.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)),
+                 passes.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)))
+    return [(distinct[begin[c]:begin[c + 1]].copy(), counts[begin[c]:begin[c + 1]].copy(), int(na[c])) +
+            ((int(passes[c]),) if sort_passes else ()) for c in range(ncol)]
 
 
 def csc_bin_launch_info():

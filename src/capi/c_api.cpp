@@ -183,13 +183,22 @@ std::vector<int> SampleRows(const Config& cfg, data_size_t nrow) {
   return rnd.Sample(nrow, cnt);
 }
 
+// LGBM_AMD_DEVICE_BIN_FIND=2 (tests): the sample's distinct values by the host evaluator of the
+// device's rule instead of FindBin's own sort
+bool EvaluatedBinFind() {
+  const char* e = tuning::Get(tuning::Knob::DeviceBinFind);
+  return e != nullptr && e[0] == '2';
+}
+
 Dataset* ConstructFromSamples(std::vector<std::vector<double>>* sv, std::vector<std::vector<int>>* si, int ncol,
-                              size_t sample_cnt, data_size_t nrow, const Config& cfg) {
+                              size_t sample_cnt, data_size_t nrow, const Config& cfg,
+                              const SampleDistinctLists* distinct = nullptr) {
   DatasetLoader loader(cfg, 1, 0);
   loader.SetHeader({});
   auto forced = DatasetLoader::GetForcedBins(cfg.forcedbins_filename, ncol, loader.categorical());
   std::unique_ptr<Dataset> ds(new Dataset(nrow));
-  ds->ConstructFromSample(sv, si, ncol, sample_cnt, nrow, cfg, loader.categorical(), loader.ignored(), forced);
+  ds->ConstructFromSample(sv, si, ncol, sample_cnt, nrow, cfg, loader.categorical(), loader.ignored(), forced,
+                          distinct);
   std::vector<std::string> names;
   for (int i = 0; i < ncol; ++i) names.push_back("Column_" + std::to_string(i));
   ds->set_feature_names(names);
@@ -875,7 +884,10 @@ int LGBM_DatasetCreateFromMat(const void* data, int data_type, int32_t nrow, int
         si[kv.first].push_back(static_cast<int>(i));
       }
     }
-    ds.reset(ConstructFromSamples(&sv, &si, ncol, idx.size(), nrow, cfg));
+    SampleDistinctLists lists;
+    const bool evaluated = EvaluatedBinFind();
+    if (evaluated) EvalSampleDistinctLists(sv, &lists);
+    ds.reset(ConstructFromSamples(&sv, &si, ncol, idx.size(), nrow, cfg, evaluated ? &lists : nullptr));
   } else {
     ds.reset(new Dataset(nrow));
     ds->CreateValid(*static_cast<const Dataset*>(reference), nrow);
@@ -933,15 +945,26 @@ int LGBM_AMD_DatasetCreateFromDeviceMat(const void* d_data, int data_type, int32
     std::vector<std::vector<double>> sv;
     std::vector<std::vector<int>> si;
     const auto idx = SampleRows(cfg, nrow);
-    SampleDeviceTensor(t, idx, &sv, &si);
-    ds.reset(ConstructFromSamples(&sv, &si, ncol, idx.size(), nrow, cfg));
+    // ... and, for a sample large enough, sorted there into each column's distinct values
+    SampleDistinctLists lists;
+    const bool on_device = UseDeviceBinFind(static_cast<int64_t>(idx.size()), ncol);
+    {
+      common::ScopedTimer timer("DeviceMat::sample");
+      SampleDeviceTensor(t, idx, &sv, &si, on_device ? &lists : nullptr);
+    }
+    const bool evaluated = !on_device && EvaluatedBinFind();
+    if (evaluated) EvalSampleDistinctLists(sv, &lists);
+    ds.reset(ConstructFromSamples(&sv, &si, ncol, idx.size(), nrow, cfg, on_device || evaluated ? &lists : nullptr));
   } else {
     ds.reset(new Dataset(nrow));
     ds->CreateValid(*static_cast<const Dataset*>(reference), nrow);
     ds->metadata().Init(nrow, false, false);
   }
-  BinDeviceTensor(ds.get(), t);
-  ds->FinishLoad();
+  {
+    common::ScopedTimer timer("DeviceMat::bin");
+    BinDeviceTensor(ds.get(), t);
+    ds->FinishLoad();
+  }
   *out = ds.release();
   API_END();
 }
@@ -1906,9 +1929,61 @@ int LGBM_AMD_TensorBinLaunchInfo(int64_t* out) {
   API_END();
 }
 
-int LGBM_AMD_DeviceBinTensorStats(int64_t* tensor_calls) {
+int LGBM_AMD_DeviceBinTensorStats(int64_t* tensor_calls, int64_t* bin_find_calls) {
   API_BEGIN();
-  DeviceBinTensorStats(tensor_calls);
+  DeviceBinTensorStats(tensor_calls, bin_find_calls);
+  API_END();
+}
+
+int LGBM_AMD_BinFindLaunchInfo(int64_t* out) {
+  API_BEGIN();
+  BinFindLaunchInfo(out);
+  API_END();
+}
+
+namespace {
+
+// the lists into the caller's arrays (distinct / counts hold up to ns * ncol entries)
+void CopyDistinctLists(const SampleDistinctLists& l, double* distinct, int32_t* counts, int64_t* begin,
+                       int32_t* nan_cnt) {
+  std::copy(l.distinct.begin(), l.distinct.end(), distinct);
+  std::copy(l.counts.begin(), l.counts.end(), counts);
+  std::copy(l.begin.begin(), l.begin.end(), begin);
+  std::copy(l.nan_cnt.begin(), l.nan_cnt.end(), nan_cnt);
+}
+
+}  // namespace
+
+int LGBM_AMD_SampleDistinct(const double* sample, int64_t ns, int32_t ncol, double* distinct, int32_t* counts,
+                            int64_t* begin, int32_t* nan_cnt) {
+  API_BEGIN();
+  if (ns < 0 || ncol < 0 || (sample == nullptr && ns * ncol > 0)) Log::Fatal("sample: null pointer or a negative size");
+  SampleDistinctLists l;
+  EvalSampleDistinctLists(sample, ns, ncol, &l);
+  CopyDistinctLists(l, distinct, counts, begin, nan_cnt);
+  API_END();
+}
+
+int LGBM_AMD_DeviceSampleDistinct(const void* d_data, int data_type, int32_t nrow, int32_t ncol, int64_t row_stride,
+                                  int64_t col_stride, int device_id, const int32_t* rows, int32_t num_rows,
+                                  double* distinct, int32_t* counts, int64_t* begin, int32_t* nan_cnt,
+                                  int32_t* sort_passes) {
+  API_BEGIN();
+  if (d_data == nullptr || nrow <= 0 || ncol <= 0) Log::Fatal("device matrix: null pointer or %d x %d", nrow, ncol);
+  if (rows != nullptr && num_rows < 0) Log::Fatal("device matrix: %d sampled rows", num_rows);
+  const DeviceTensor t{d_data, data_type, nrow, ncol, row_stride, col_stride, device_id};
+  std::vector<int> idx;
+  if (rows != nullptr) {
+    idx.assign(rows, rows + num_rows);
+  } else {
+    for (int32_t r = 0; r < nrow; ++r) idx.push_back(r);
+  }
+  std::vector<std::vector<double>> sv;
+  std::vector<std::vector<int>> si;
+  SampleDistinctLists l;
+  SampleDeviceTensor(t, idx, &sv, &si, &l);
+  CopyDistinctLists(l, distinct, counts, begin, nan_cnt);
+  if (sort_passes != nullptr) std::copy(l.sort_passes.begin(), l.sort_passes.end(), sort_passes);
   API_END();
 }
 

@@ -39,9 +39,11 @@
 #include <algorithm>
 #include <atomic>
 #include <cmath>
+#include <memory>
 #include <utility>
 #include <vector>
 
+#include "bin_find.h"
 #include "group_bin_scratch.h"
 #include "lgbm_amd/c_api.h"
 #include "lgbm_amd/common.h"
@@ -49,6 +51,9 @@
 #include "lgbm_amd/device_binning.h"
 #include "lgbm_amd/log.h"
 #include "lgbm_amd/meta.h"
+#include "lgbm_amd/network.h"
+#include "lgbm_amd/tuning.h"
+#include "sample_distinct.h"
 #include "tensor_bins.h"
 
 namespace lgbm_amd {
@@ -319,8 +324,9 @@ std::atomic<int64_t> g_tensor_calls{0};
 
 }  // namespace
 
-void DeviceBinTensorStats(int64_t* tensor_calls) {
+void DeviceBinTensorStats(int64_t* tensor_calls, int64_t* bin_find_calls) {
   if (tensor_calls != nullptr) *tensor_calls = g_tensor_calls.load(std::memory_order_relaxed);
+  if (bin_find_calls != nullptr) *bin_find_calls = DeviceBinFindCalls();
 }
 
 void TensorBinLaunchInfo(int64_t* out) {
@@ -331,23 +337,64 @@ void TensorBinLaunchInfo(int64_t* out) {
   out[4] = kTensorBinMinValues;
 }
 
+bool UseDeviceBinFind(int64_t sample_cnt, int64_t ncol) {
+  if (tuning::Off(tuning::Knob::DeviceBinFind) || Network::num_machines() > 1) return false;
+  return tuning::On(tuning::Knob::DeviceBinFind) ||
+         (sample_cnt >= kBinFindMinSampleRows && sample_cnt * ncol <= kBinFindMaxSampleValues);
+}
+
+namespace {
+
+void AppendEvaluatedColumn(const double* col, int64_t n, SampleDistinctLists* out) {
+  std::vector<double> d;
+  std::vector<int32_t> c;
+  out->nan_cnt.push_back(dev::EvalSampleDistinct(col, n, &d, &c));
+  int kept = 0;
+  for (int32_t v : c) kept += v;
+  out->num_values.push_back(kept);
+  out->distinct.insert(out->distinct.end(), d.begin(), d.end());
+  out->counts.insert(out->counts.end(), c.begin(), c.end());
+  out->begin.push_back(static_cast<int64_t>(out->distinct.size()));
+}
+
+}  // namespace
+
+void EvalSampleDistinctLists(const double* sample, int64_t ns, int32_t ncol, SampleDistinctLists* out) {
+  *out = SampleDistinctLists();
+  for (int32_t j = 0; j < ncol; ++j) AppendEvaluatedColumn(sample + static_cast<int64_t>(j) * ns, ns, out);
+}
+
+void EvalSampleDistinctLists(const std::vector<std::vector<double>>& columns, SampleDistinctLists* out) {
+  *out = SampleDistinctLists();
+  for (const auto& v : columns) AppendEvaluatedColumn(v.data(), static_cast<int64_t>(v.size()), out);
+}
+
 void SampleDeviceTensor(const DeviceTensor& t, const std::vector<int>& rows, std::vector<std::vector<double>>* sv,
-                        std::vector<std::vector<int>>* si) {
+                        std::vector<std::vector<int>>* si, SampleDistinctLists* distinct) {
   CheckTensor(t);
   sv->assign(static_cast<size_t>(t.ncol), {});
   si->assign(static_cast<size_t>(t.ncol), {});
   const int ns = static_cast<int>(rows.size());
-  if (ns == 0) return;
+  if (ns == 0) {
+    if (distinct != nullptr) EvalSampleDistinctLists(nullptr, 0, t.ncol, distinct);
+    return;
+  }
   for (int r : rows) {
     if (r < 0 || r >= t.nrow) Log::Fatal("device matrix: sampled row %d outside %d rows", r, t.nrow);
   }
   DeviceScope sc;
   sc.Enter(t.device_id);
   const int32_t* d_idx = sc.Upload(std::vector<int32_t>(rows.begin(), rows.end()));
-  // columns per pass: at most ~256 MiB of doubles, whole column tiles
-  const int64_t fit = kChunkBytes / (static_cast<int64_t>(sizeof(double)) * ns);
+  // columns per pass: at most ~256 MiB of doubles (and of the sort's scratch), whole column tiles
+  const int64_t cell = static_cast<int64_t>(sizeof(double)) + (distinct != nullptr ? kBinFindScratchBytes : 0);
+  const int64_t fit = kChunkBytes / (cell * ns);
   const int pass = static_cast<int>(std::min<int64_t>(t.ncol, std::max<int64_t>(kGatherTile, fit / kGatherTile * kGatherTile)));
   double* d_out = sc.Alloc<double>(static_cast<size_t>(pass) * ns);
+  std::unique_ptr<DeviceSampleDistinct> finder;
+  if (distinct != nullptr) {
+    *distinct = SampleDistinctLists();
+    finder.reset(new DeviceSampleDistinct(pass, ns));
+  }
   std::vector<double> h(static_cast<size_t>(pass) * ns);
   const int ntile_s = (ns + kGatherTile - 1) / kGatherTile;
   for (int c0 = 0; c0 < t.ncol; c0 += pass) {
@@ -361,6 +408,7 @@ void SampleDeviceTensor(const DeviceTensor& t, const std::vector<int>& rows, std
     });
     GROUPBINCHECK(hipGetLastError());
     GROUPBINCHECK(hipMemcpy(h.data(), d_out, sizeof(double) * static_cast<size_t>(nc) * ns, hipMemcpyDeviceToHost));
+    if (finder != nullptr) finder->Launch(d_out, nc);  // (sorts d_out in place while the host filters its copy)
     // the zero / NaN filter of the host's row reader (DenseRowPairFun), sample positions ascending
 #pragma omp parallel for schedule(static)
     for (int c = 0; c < nc; ++c) {
@@ -374,7 +422,9 @@ void SampleDeviceTensor(const DeviceTensor& t, const std::vector<int>& rows, std
         }
       }
     }
+    if (finder != nullptr) finder->Collect(distinct);
   }
+  if (distinct != nullptr) NoteDeviceBinFind();
 }
 
 void BinDeviceTensor(Dataset* ds, const DeviceTensor& t) {

@@ -209,55 +209,82 @@ BinMapper::BinMapper()
   bin_upper_bound_.push_back(kInf);
 }
 
-void BinMapper::FindBin(double* values, int num_values, size_t total_sample_cnt, int max_bin, int min_data_in_bin,
-                        int min_split_data, bool pre_filter, BinType bin_type, bool use_missing,
-                        bool zero_as_missing, const std::vector<double>& forced_upper_bounds) {
+int BinMapper::SampleDistinct(double* values, int num_values, std::vector<double>* distinct, std::vector<int>* counts,
+                              int* nan_cnt) {
   // drop NaNs (counted separately)
   int kept = 0;
   for (int i = 0; i < num_values; ++i) {
     if (!std::isnan(values[i])) values[kept++] = values[i];
   }
+  *nan_cnt = num_values - kept;
+  num_values = kept;
+  std::stable_sort(values, values + num_values);
+  distinct->clear();
+  counts->clear();
+  for (int i = 0; i < num_values; ++i) {
+    if (i == 0 || !common::CheckDoubleEqualOrdered(values[i - 1], values[i])) {
+      distinct->push_back(values[i]);
+      counts->push_back(1);
+    } else {
+      distinct->back() = values[i];  // keep the larger of near-equal values
+      ++counts->back();
+    }
+  }
+  return num_values;
+}
+
+void BinMapper::FindBin(double* values, int num_values, size_t total_sample_cnt, int max_bin, int min_data_in_bin,
+                        int min_split_data, bool pre_filter, BinType bin_type, bool use_missing,
+                        bool zero_as_missing, const std::vector<double>& forced_upper_bounds) {
+  std::vector<double> distinct;
+  std::vector<int> counts;
+  int nan_cnt = 0;
+  const int kept = SampleDistinct(values, num_values, &distinct, &counts, &nan_cnt);
+  FindBinFromDistinct(distinct.data(), counts.data(), static_cast<int>(distinct.size()), kept, nan_cnt,
+                      total_sample_cnt, max_bin, min_data_in_bin, min_split_data, pre_filter, bin_type, use_missing,
+                      zero_as_missing, forced_upper_bounds);
+}
+
+void BinMapper::FindBinFromDistinct(const double* sample_distinct, const int* sample_counts, int num_distinct,
+                                    int num_values, int nan_cnt, size_t total_sample_cnt, int max_bin,
+                                    int min_data_in_bin, int min_split_data, bool pre_filter, BinType bin_type,
+                                    bool use_missing, bool zero_as_missing,
+                                    const std::vector<double>& forced_upper_bounds) {
   int na_cnt = 0;
   if (!use_missing) {
     missing_type_ = MissingType::None;
   } else if (zero_as_missing) {
     missing_type_ = MissingType::Zero;
-  } else if (kept == num_values) {
+  } else if (nan_cnt == 0) {
     missing_type_ = MissingType::None;
   } else {
     missing_type_ = MissingType::NaN;
-    na_cnt = num_values - kept;
+    na_cnt = nan_cnt;
   }
-  num_values = kept;
   bin_type_ = bin_type;
   default_bin_ = 0;
   const int zero_cnt = static_cast<int>(total_sample_cnt - num_values - na_cnt);
 
-  std::stable_sort(values, values + num_values);
+  // the zero entry: before the first positive value, between a negative and a positive
+  // neighbour, or behind the last negative value (the sample holds no zeros, so the two
+  // neighbours are never one run)
   std::vector<double> distinct;
   std::vector<int> counts;
-  if (num_values == 0 || (values[0] > 0.0 && zero_cnt > 0)) {
+  distinct.reserve(static_cast<size_t>(num_distinct) + 1);
+  counts.reserve(static_cast<size_t>(num_distinct) + 1);
+  if (num_distinct == 0 || (sample_distinct[0] > 0.0 && zero_cnt > 0)) {
     distinct.push_back(0.0);
     counts.push_back(zero_cnt);
   }
-  if (num_values > 0) {
-    distinct.push_back(values[0]);
-    counts.push_back(1);
-  }
-  for (int i = 1; i < num_values; ++i) {
-    if (!common::CheckDoubleEqualOrdered(values[i - 1], values[i])) {
-      if (values[i - 1] < 0.0 && values[i] > 0.0) {
-        distinct.push_back(0.0);
-        counts.push_back(zero_cnt);
-      }
-      distinct.push_back(values[i]);
-      counts.push_back(1);
-    } else {
-      distinct.back() = values[i];  // keep the larger of near-equal values
-      ++counts.back();
+  for (int i = 0; i < num_distinct; ++i) {
+    if (i > 0 && sample_distinct[i - 1] < 0.0 && sample_distinct[i] > 0.0) {
+      distinct.push_back(0.0);
+      counts.push_back(zero_cnt);
     }
+    distinct.push_back(sample_distinct[i]);
+    counts.push_back(sample_counts[i]);
   }
-  if (num_values > 0 && values[num_values - 1] < 0.0 && zero_cnt > 0) {
+  if (num_distinct > 0 && sample_distinct[num_distinct - 1] < 0.0 && zero_cnt > 0) {
     distinct.push_back(0.0);
     counts.push_back(zero_cnt);
   }

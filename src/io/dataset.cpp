@@ -216,9 +216,14 @@ void Dataset::ConstructFromSample(std::vector<std::vector<double>>* sample_value
                                   std::vector<std::vector<int>>* sample_indices, int num_col,
                                   size_t total_sample_cnt, data_size_t num_data, const Config& cfg,
                                   const std::unordered_set<int>& categorical, const std::unordered_set<int>& ignored,
-                                  const std::vector<std::vector<double>>& forced_bins) {
+                                  const std::vector<std::vector<double>>& forced_bins,
+                                  const SampleDistinctLists* distinct) {
   num_data_ = num_data;
   std::vector<std::unique_ptr<BinMapper>> mappers(num_col);
+  if (Network::num_machines() > 1) distinct = nullptr;  // (each rank sorts its block of columns)
+  // thread time of FindBin's two halves under LGBM_AMD_TIMETAG=1 (tools/bench_tensor_dataset.py)
+  const bool timed = common::PhaseTimer::Global().enabled();
+  double sort_ms = 0.0, search_ms = 0.0;
   if (!cfg.max_bin_by_feature.empty()) {
     LGBM_CHECK_EQ(static_cast<int>(cfg.max_bin_by_feature.size()), num_col);
   }
@@ -237,6 +242,7 @@ void Dataset::ConstructFromSample(std::vector<std::vector<double>>* sample_value
     col_begin = std::min(num_col, step * rank);
     col_end = std::min(num_col, col_begin + step);
   }
+  const double loop_start = timed ? common::NowSeconds() : 0.0;
 #pragma omp parallel for schedule(guided)
   for (int i = col_begin; i < col_end; ++i) {
     if (ignored.count(i)) continue;
@@ -251,13 +257,48 @@ void Dataset::ConstructFromSample(std::vector<std::vector<double>>* sample_value
     }
     mappers[i].reset(new BinMapper());
     int mb = cfg.max_bin_by_feature.empty() ? cfg.max_bin : cfg.max_bin_by_feature[i];
-    std::vector<double> vals = (*sample_values)[i];
     static const std::vector<double> kNoForced;
     const std::vector<double>& fb = i < static_cast<int>(forced_bins.size()) ? forced_bins[i] : kNoForced;
     errors.Run([&] {
-      mappers[i]->FindBin(vals.data(), static_cast<int>(vals.size()), total_sample_cnt, mb, cfg.min_data_in_bin,
-                          filter_cnt, cfg.feature_pre_filter, t, cfg.use_missing, cfg.zero_as_missing, fb);
+      // FindBin's two halves; the first is skipped where its result was handed in
+      std::vector<double> vals, own_distinct;
+      std::vector<int> own_counts;
+      const double* dv;
+      const int* dc;
+      int nd, kept, nan_cnt = 0;
+      const double t0 = timed ? common::NowSeconds() : 0.0;
+      if (distinct != nullptr) {
+        const int64_t b = distinct->begin[i];
+        dv = distinct->distinct.data() + b;
+        dc = distinct->counts.data() + b;
+        nd = static_cast<int>(distinct->begin[i + 1] - b);
+        kept = distinct->num_values[i];
+        nan_cnt = distinct->nan_cnt[i];
+      } else {
+        vals = (*sample_values)[i];
+        kept = BinMapper::SampleDistinct(vals.data(), static_cast<int>(vals.size()), &own_distinct, &own_counts,
+                                         &nan_cnt);
+        dv = own_distinct.data();
+        dc = own_counts.data();
+        nd = static_cast<int>(own_distinct.size());
+      }
+      const double t1 = timed ? common::NowSeconds() : 0.0;
+      mappers[i]->FindBinFromDistinct(dv, dc, nd, kept, nan_cnt, total_sample_cnt, mb, cfg.min_data_in_bin,
+                                      filter_cnt, cfg.feature_pre_filter, t, cfg.use_missing, cfg.zero_as_missing,
+                                      fb);
+      if (timed) {
+        const double d0 = (t1 - t0) * 1e3, d1 = (common::NowSeconds() - t1) * 1e3;
+#pragma omp atomic
+        sort_ms += d0;
+#pragma omp atomic
+        search_ms += d1;
+      }
     });
+  }
+  if (timed) {
+    common::PhaseTimer::Global().Add("Dataset::find_bins", (common::NowSeconds() - loop_start) * 1e3);
+    common::PhaseTimer::Global().Add("Dataset::find_bins/sort_thread_time", sort_ms);
+    common::PhaseTimer::Global().Add("Dataset::find_bins/search_thread_time", search_ms);
   }
   errors.Check();
   if (!err.empty()) Log::Fatal("%s", err.c_str());
@@ -300,6 +341,7 @@ void Dataset::ConstructFromSample(std::vector<std::vector<double>>* sample_value
     }
   }
   forced_bin_bounds_ = forced_bins;
+  common::ScopedTimer bundle_timer("Dataset::bundle_and_layout");
   ConstructFromBinMappers(&mappers, num_data, cfg, sample_indices, sample_values, total_sample_cnt);
 }
 

@@ -14,6 +14,16 @@ construction covers the device work.  The two alternate inside one run after a w
 the median and every time of --repeats are reported.  "equal" tells whether both ways saved the
 same binary file (checked on the smallest sweep entry).  Prints one JSON line.
 
+With --bin-find the tool measures the training set of the device way alone, with the first step of
+the bin finder (the sort of each column's sample and its distinct values) on the host
+(LGBM_AMD_DEVICE_BIN_FIND=0: the path before src/device/bin_find_kernels.hip) and on the device (=1),
+alternating, for --shapes and for --gate entries (rows x cols with rows below
+bin_construct_sample_cnt, so that rows is the sample size).  Host timers (LGBM_AMD_TIMETAG=1,
+lgb.get_timers) split each construction into: sample (gather, copy and zero filter; with =1 also the
+wait for the device sort and the copy of the runs), sort and search (the wall time of the bin-finder
+loop, divided by the thread time its two halves took; with =1 the loop is the search alone), bundle
+(feature bundling and the dataset's layout) and bin (the binning of the whole tensor).
+
   python tools/bench_tensor_dataset.py
   python tools/bench_tensor_dataset.py --shapes --sweep 1000 10000 100000
 """
@@ -34,7 +44,11 @@ def main():
     ap.add_argument("--sweep", nargs="*", type=int, default=[1_000, 10_000, 100_000, 1_000_000])
     ap.add_argument("--repeats", type=int, default=3)
     ap.add_argument("--host-threads", type=int, default=16)
+    ap.add_argument("--bin-find", action="store_true")
+    ap.add_argument("--gate", nargs="*", default=[])
     args = ap.parse_args()
+    if args.bin_find:
+        os.environ["LGBM_AMD_TIMETAG"] = "1"  # (read when the library first looks at its timers)
 
     import torch
 
@@ -95,6 +109,43 @@ def main():
                 with open(f, "rb") as fh:
                     files.append(fh.read())
         return files[0] == files[1]
+
+    def phases(before, after):
+        d = {k: after.get(k, 0.0) - before.get(k, 0.0) for k in after}
+        loop, sort, search = (d.get("Dataset::find_bins" + k, 0.0) for k in ("", "/sort_thread_time", "/search_thread_time"))
+        share = sort / (sort + search) if sort + search > 0 else 0.0
+        return {"sample": d.get("DeviceMat::sample", 0.0), "sort": loop * share, "search": loop * (1 - share),
+                "bundle": d.get("Dataset::bundle_and_layout", 0.0), "bin": d.get("DeviceMat::bin", 0.0)}
+
+    def measure_bin_find(X):
+        out = {"rows": X.shape[0], "cols": X.shape[1]}
+        runs = {"0": [], "1": []}
+        for rep in range(args.repeats + 1):
+            for knob in ("0", "1"):
+                os.environ["LGBM_AMD_DEVICE_BIN_FIND"] = knob
+                calls, timers = ops.tensor_bin_stats(bin_find=True), lgb.get_timers()
+                dt, train = build(X, "device", False)
+                if (ops.tensor_bin_stats(bin_find=True) != calls) != (knob == "1"):
+                    raise SystemExit("LGBM_AMD_DEVICE_BIN_FIND=%s did not run as asked" % knob)
+                if rep > 0:
+                    runs[knob].append(dict(phases(timers, lgb.get_timers()), total=dt))
+                del train
+        os.environ.pop("LGBM_AMD_DEVICE_BIN_FIND", None)
+        for knob, name in (("0", "host_sort"), ("1", "device_sort")):
+            out[name + "_s"] = {k: round(statistics.median(r[k] for r in runs[knob]), 5) for k in runs[knob][0]}
+            out[name + "_all"] = [round(r["total"], 5) for r in runs[knob]]
+        print(json.dumps(out), file=sys.stderr, flush=True)
+        return out
+
+    if args.bin_find:
+        result = {"tool": "bench_tensor_dataset --bin-find", "host_threads": args.host_threads,
+                  "repeats": args.repeats, "shapes": [], "gate": []}
+        for k, shape in enumerate(args.shapes + args.gate):
+            rows, cols = (int(v) for v in shape.split("x"))
+            result["shapes" if k < len(args.shapes) else "gate"].append(measure_bin_find(make(rows, cols, False, 1 + k)))
+            torch.cuda.empty_cache()
+        print(json.dumps(result))
+        return
 
     result = {"tool": "bench_tensor_dataset", "host_threads": args.host_threads, "repeats": args.repeats,
               "shapes": [], "sweep": []}
