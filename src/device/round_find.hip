@@ -6,10 +6,21 @@ namespace lgbm_amd {
 namespace dev {
 
 // ----------------------------------------------------------------------------- k_round_find
+// a per-feature record as the 8-byte words it is published in (PublishRecord)
+constexpr int kFbWords = static_cast<int>(sizeof(FeatureBest) / 8);
+static_assert(__builtin_offsetof(FeatureBest, gain) == 0 && __builtin_offsetof(FeatureBest, feature) == 56 &&
+                  __builtin_offsetof(FeatureBest, real_feature) == 60 && __builtin_offsetof(FeatureBest, ncat) == 84,
+              "FbGain / FbFeature / FbRealFeature / FbNcat");
+__device__ __forceinline__ double FbGain(const unsigned long long* w) { return __longlong_as_double(static_cast<long long>(w[0])); }
+__device__ __forceinline__ int FbFeature(const unsigned long long* w) { return static_cast<int>(static_cast<uint32_t>(w[7])); }
+__device__ __forceinline__ int FbRealFeature(const unsigned long long* w) { return static_cast<int>(static_cast<uint32_t>(w[7] >> 32)); }
+__device__ __forceinline__ int FbNcat(const unsigned long long* w) { return static_cast<int16_t>(static_cast<uint16_t>(w[10] >> 32)); }
+
 template <int KIND, int NT>
 struct RoundFindShared {
   ScanShared<KIND, NT> scan;
   ArgC arg[NT / kWave];  // ChildBest's per-wave winners
+  unsigned long long rec[NT / kWave][kFbWords];  // and their whole records, where a thread's first feature won its wave
 };
 
 // the best split of child y (2j + lr) of the round, node `node`, from its per-feature
@@ -22,8 +33,25 @@ __device__ inline void ChildBest(const KArgs& a, int y, int node, RoundFindShare
   const FeatureBest* fb0 = a.feat_best;
   constexpr int kB = 8;
   ArgC c = ArgNone();
+  // a thread's first feature comes with its whole record (registers: words, not the struct,
+  // which would live in scratch): the winner's copy is then handed over through LDS instead of
+  // loaded again, a dependent global round trip after the argmax.  NT features cover every
+  // child but those of very wide data, whose later winners are loaded again below.
+  unsigned long long mine[kFbWords];
+#pragma unroll
+  for (int i = 0; i < kFbWords; ++i) mine[i] = 0ull;
+  if (tid < NF) {
+    const unsigned long long* src = reinterpret_cast<const unsigned long long*>(fb0 + RoundFbIndex(a, y, tid));
+#pragma unroll
+    for (int i = 0; i < kFbWords; ++i) mine[i] = src[i];
+    if (FbFeature(mine) >= 0) {
+      c.g = FbGain(mine);
+      c.rf = FbRealFeature(mine);
+      c.idx = tid;
+    }
+  }
 #pragma unroll 1
-  for (int i0 = tid; i0 < NF; i0 += kB * NT) {
+  for (int i0 = tid + NT; i0 < NF; i0 += kB * NT) {
     double cg[kB];
     int crf[kB], cf[kB];
 #pragma unroll
@@ -48,6 +76,10 @@ __device__ inline void ChildBest(const KArgs& a, int y, int node, RoundFindShare
   }
   c = ArgWaveBest(c);
   if ((tid & 63) == 0) sh.arg[tid >> 6] = c;
+  if (c.idx == tid) {  // (a first feature: the wave's winner is this thread's)
+#pragma unroll
+    for (int i = 0; i < kFbWords; ++i) sh.rec[tid >> 6][i] = mine[i];
+  }
   __syncthreads();
   ArgC b = sh.arg[0];
 #pragma unroll
@@ -58,9 +90,15 @@ __device__ inline void ChildBest(const KArgs& a, int y, int node, RoundFindShare
   if (tid == 0) {
     if (b.idx >= 0 && b.g != -INFINITY) {
       const size_t wi = RoundFbIndex(a, y, b.idx);
-      const FeatureBest w = fb0[wi];
-      PublishRecord(dst, w);
-      if (w.ncat > 0) {
+      // (an index below NT is the thread that held it as its first feature: its wave's record)
+      const unsigned long long* src = b.idx < NT ? sh.rec[b.idx >> 6] : reinterpret_cast<const unsigned long long*>(fb0 + wi);
+      unsigned long long w[kFbWords];
+#pragma unroll
+      for (int i = 0; i < kFbWords; ++i) w[i] = src[i];
+      GlobalU64* d = (GlobalU64*)(dst);
+#pragma unroll
+      for (int i = 0; i < kFbWords; ++i) __hip_atomic_store(d + i, w[i], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      if (FbNcat(w) > 0) {
         PublishCatCopy(a.cbest_cat + ci * kMaxCatWords, a.feat_cat + wi * kMaxCatWords);
       }
     } else {

@@ -1107,26 +1107,9 @@ __device__ inline void RoundPlanBody(const KArgs& a, unsigned char* plan_lds) {
       s_c[2 * j + 1] = C;
     }
   }
-  stamp(19);
-  if (s_done) {
-    if (tid == 0) {
-      rd->done = 1;
-      rd->nsplit = s1;
-      rd->nexp = 0;
-      rd->accepted_max = max(accmax0, nacc);
-    }
-    if (a.host_out != nullptr) {
-      __syncthreads();  // (this plan's records are written)
-      HostTreeOut(a, s1, rounds0, nn, s_draw);
-    }
-    return;
-  }
-  __syncthreads();
-  stamp(20);
-  if (tid < kWave) {
-    // row blocks: one size for the round (at least blk_min_rows, at most the packed headroom),
-    // one lane per expansion
-    const int pcj = lane < nexp ? s_pc[lane] : 0;
+  // row blocks: one size for the round (at least blk_min_rows, at most the packed headroom),
+  // one lane per expansion (a whole wave; pcj: the rows of the lane's expansion)
+  auto size_blocks = [&](const int pcj) {
     const unsigned urows = static_cast<unsigned>(WaveSum(pcj));
     // balanced over the grid: the smallest m with blocks of ceil(rows / (m * grid - nexp))
     // rows under the packed headroom; every workgroup then takes m blocks at most (one
@@ -1159,7 +1142,31 @@ __device__ inline void RoundPlanBody(const KArgs& a, unsigned char* plan_lds) {
       rd->rounds = rounds0 + 1;
       rd->accepted_max = max(accmax0, nacc);
     }
+  };
+  // (the sizing needs the picks' row counts only: wave 1 loads them itself and sizes the blocks
+  // while wave 0 composes the plans, instead of after them and a barrier -- 0.6 us of the one
+  // workgroup's serial path; a one-wave plan sizes after its plans as before)
+  constexpr bool kSizeBeside = NT > kWave;
+  if (kSizeBeside && nent > 0 && tid >= kWave && tid < 2 * kWave) {
+    size_blocks(lane < nexp ? a.rnode[s_pick[lane]].count : 0);
   }
+  stamp(19);
+  if (s_done) {
+    if (tid == 0) {
+      rd->done = 1;
+      rd->nsplit = s1;
+      rd->nexp = 0;
+      rd->accepted_max = max(accmax0, nacc);
+    }
+    if (a.host_out != nullptr) {
+      __syncthreads();  // (this plan's records are written)
+      HostTreeOut(a, s1, rounds0, nn, s_draw);
+    }
+    return;
+  }
+  if constexpr (!kSizeBeside) __syncthreads();
+  stamp(20);
+  if constexpr (!kSizeBeside) size_blocks(lane < nexp ? s_pc[lane] : 0);
   if (tid < kMaxRoundExp) {
     rd->cur[tid][0] = rd->cur[tid][1] = 0;
     rd->loc_acc[tid][0] = rd->loc_acc[tid][1] = 0ull;
