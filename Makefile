@@ -44,6 +44,8 @@ $(BUILD)/device/tensor_bin_kernels.hip.o: HIPEXTRA += -Xclang -target-feature -X
 # (the sort moves the bits of doubles and computes nothing in floating point: the flag only keeps
 # the rule that new device code is built without those instructions)
 $(BUILD)/device/bin_find_kernels.hip.o: HIPEXTRA += -Xclang -target-feature -Xclang -packed-fp32-ops
+# (the prediction of device matrices: its sums and transforms are compared bit for bit with the host's)
+$(BUILD)/device/tensor_predict_kernels.hip.o: HIPEXTRA += -Xclang -target-feature -Xclang -packed-fp32-ops
 
 $(LIB): $(HOST_OBJS) $(DEV_OBJS)
 	@mkdir -p $(LIBDIR)

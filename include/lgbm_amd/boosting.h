@@ -141,6 +141,21 @@ class GBDT {
   // memory (raw scores, leaf indices or contributions); what is not applicable is an error
   void PredictDeviceBuffers(const void* d_data, bool is_double, int64_t nrow, int ncol, int start_iteration,
                             int num_iteration, DevicePredictKind kind, double* d_out, int64_t out_len);
+  // every kind of prediction, Normal included, of a strided matrix in the memory of HIP device
+  // device_id (element (r, c) at d_data[r * row_stride + c * col_stride] of the C API's data_type
+  // float32 / float64 / float16 / bfloat16) into out_len doubles of that device's memory, as
+  // Predict / PredictRaw / PredictLeafIndex / PredictContrib give them for the values as float64.
+  // src/device/tensor_predict.h plans the route: the tile kernel, or the compact matrix of the
+  // sparse paths in chunks of rows.  Runs on the device's null stream, restores the caller's device
+  // and returns when the data is complete; what is not applicable is an error
+  void PredictDeviceTensor(const void* d_data, int data_type, int64_t nrow, int ncol, int64_t row_stride,
+                           int64_t col_stride, int device_id, DevicePredictKind kind, int start_iteration,
+                           int num_iteration, double* d_out, int64_t out_len);
+  // the same plan, tile and packed-node walk evaluated on a host matrix of that description
+  // (tests; needs no device): Normal, Raw or Leaf into out_len doubles
+  void TensorPredictOnHost(const void* data, int data_type, int64_t nrow, int ncol, int64_t row_stride,
+                           int64_t col_stride, DevicePredictKind kind, int start_iteration, int num_iteration,
+                           double* out, int64_t out_len);
   // the same predictions of the rows of a host CSR matrix (indptr int32 / int64, nindptr = rows +
   // 1 entries): each chunk of rows is scattered on the device into a compact matrix of the
   // features the window's trees split on, which the same kernels walk.  Absent entries are 0,
@@ -312,6 +327,12 @@ class GBDT {
   template <typename Forest>
   void UploadForDeviceBuffers(Forest* forest, DevicePredictKind kind, bool slots, int64_t nrow, int64_t out_len,
                               int start_iteration, int num_iteration);
+  // ... and PredictDeviceTensor / TensorPredictOnHost, after InitPredict: the checks of the matrix,
+  // the column and class counts, and into `a` (dev::TensorPredictArgs) the strides, the kind and
+  // what the host predictor does to a row of raw scores
+  template <typename Args>
+  void TensorPredictChecks(const void* data, int64_t nrow, int ncol, int64_t row_stride, int64_t col_stride,
+                           DevicePredictKind kind, Args* a);
   int num_init_iteration_ = 0;
   std::vector<std::string> feature_names_;
   std::vector<std::string> feature_infos_;

@@ -400,6 +400,38 @@ LIGHTGBM_C_EXPORT int LGBM_AMD_DeviceBinCscStats(int64_t* csc_calls, int64_t* co
 // predictions this process has computed on the device, over all boosters (tests: whether a call
 // took the device path or the host predictor)
 LIGHTGBM_C_EXPORT int LGBM_AMD_DevicePredictCount(int64_t* out);
+// Predictions of a matrix in device memory, read where it lies and written to device memory
+// (src/device/tensor_predict_kernels.hip): the matrix is described as for
+// LGBM_AMD_DatasetCreateFromDeviceMat (nrow is 64-bit here), predict_type / start_iteration /
+// num_iteration as for LGBM_BoosterPredictForMat, and d_out holds out_len = nrow * the width of
+// LGBM_BoosterCalcNumPredict doubles on the same device, row-major (anything else is an error).
+// C_API_PREDICT_NORMAL applies on the device what the host predictor applies to raw scores: the
+// average of boosting=rf and the objective's output transform (ObjectiveFunction::DeviceOutputKind;
+// no objective: raw scores).  Any booster, any number of rows; a column count other than the
+// model's or more than 16 trees per iteration is an error.  Runs on device_id's null stream (the
+// caller has finished its own writes of the matrix), restores the caller's device, returns when the
+// data is complete, and counts as one device prediction (LGBM_AMD_DevicePredictCount)
+LIGHTGBM_C_EXPORT int LGBM_AMD_BoosterPredictForDeviceMat(BoosterHandle handle, const void* d_data, int data_type,
+                                                          int64_t nrow, int32_t ncol, int64_t row_stride,
+                                                          int64_t col_stride, int device_id, int predict_type,
+                                                          int start_iteration, int num_iteration, double* d_out,
+                                                          int64_t out_len);
+// the rule of that path (src/device/tensor_predict.h: plan, tile, packed nodes, walk, finish)
+// evaluated on the host for a host matrix of the same description (no GPU): normal, raw or leaf
+LIGHTGBM_C_EXPORT int LGBM_AMD_TensorPredictOnHost(BoosterHandle handle, const void* data, int data_type,
+                                                   int64_t nrow, int32_t ncol, int64_t row_stride,
+                                                   int64_t col_stride, int predict_type, int start_iteration,
+                                                   int num_iteration, double* out, int64_t out_len);
+// its plan, a pure function (no GPU): a window of trees that splits on num_slots distinct features,
+// elements of elem_size bytes (2, 4, 8), the most leaves of a tree and the predict type give
+// out[0] the route (0: the tile kernel, 1: the compact slot matrix and the forest kernels of the
+// sparse paths) and out[1] the rows of a tile
+LIGHTGBM_C_EXPORT int LGBM_AMD_TensorPredictPlan(int32_t num_slots, int32_t elem_size, int32_t max_leaves,
+                                                 int predict_type, int32_t* out);
+// its launch shape (tests place shapes on the boundaries; out has room for 8 values): out[0] = n the
+// steps of the ladder of tile heights, out[1..n] the heights, tallest first, out[n + 1] the LDS
+// bytes a tile may take, out[n + 2] the most leaves of a tree whose nodes are packed
+LIGHTGBM_C_EXPORT int LGBM_AMD_TensorPredictLaunchInfo(int64_t* out);
 // ---- custom objectives and metrics on device tensors (a booster trained with device_type=gpu)
 // the HIP device of the booster's device learner, or -1 (a CPU booster, a loaded model)
 LIGHTGBM_C_EXPORT int LGBM_AMD_BoosterDeviceId(BoosterHandle handle, int* out);

@@ -1338,6 +1338,37 @@ class Booster:
         return self._to_predictor(copy.deepcopy(kwargs)).predict(
             data, start_iteration, num_iteration, raw_score, pred_leaf, pred_contrib, data_has_header, is_reshape)
 
+    def predict_device(self, data, start_iteration=0, num_iteration=None, raw_score=False, pred_leaf=False,
+                       pred_contrib=False):
+        """Predictions for the rows of a GPU tensor, computed where it lies and left there: ``data`` is
+        a non-empty 2-D float16, bfloat16, float32 or float64 torch tensor on a GPU with any
+        non-negative strides; the result is a float64 tensor ``[n, width]`` on the same device, with
+        the values and widths of :meth:`predict` (scores go through the objective's output
+        transform on the device unless ``raw_score``).  Any booster and any number of rows; neither
+        rows nor results pass through the host (src/device/tensor_predict_kernels.hip)."""
+        import torch
+        if not (_is_gpu_tensor(data) and data.dim() == 2 and str(data.dtype) in _DEVICE_MAT_CODES
+                and data.numel() > 0):
+            raise LightGBMError("predict_device needs a non-empty 2-D float16, bfloat16, float32 or float64 "
+                                "torch tensor on a GPU")
+        if num_iteration is None:
+            num_iteration = self.best_iteration if start_iteration <= 0 else -1
+        ptype = (nat.PREDICT_CONTRIB if pred_contrib else nat.PREDICT_LEAF_INDEX if pred_leaf
+                 else nat.PREDICT_RAW_SCORE if raw_score else nat.PREDICT_NORMAL)
+        t = data.detach()
+        n = t.shape[0]
+        width = ctypes.c_int64(0)
+        nat.call("LGBM_BoosterCalcNumPredict", self.handle, nat.c_int(1), nat.c_int(ptype), nat.c_int(start_iteration),
+                 nat.c_int(num_iteration), ctypes.byref(width))
+        out = torch.empty((n, width.value), dtype=torch.float64, device=t.device)
+        torch.cuda.synchronize(t.device)  # (the caller's writes of the tensor; the library uses the null stream)
+        nat.call("LGBM_AMD_BoosterPredictForDeviceMat", self.handle, ctypes.c_void_p(t.data_ptr()),
+                 nat.c_int(_DEVICE_MAT_CODES[str(t.dtype)]), ctypes.c_int64(n), ctypes.c_int32(t.shape[1]),
+                 ctypes.c_int64(t.stride(0)), ctypes.c_int64(t.stride(1)), nat.c_int(t.device.index),
+                 nat.c_int(ptype), nat.c_int(start_iteration), nat.c_int(num_iteration),
+                 ctypes.c_void_p(out.data_ptr()), ctypes.c_int64(out.numel()))
+        return out
+
     def refit(self, data, label, decay_rate=0.9, **kwargs):
         """A copy of the model with leaf values refitted on new data."""
         if self._objective_none:

@@ -49,7 +49,7 @@ import numpy as np
 from .._native import LightGBMError, call as _native_call, params_str as param_dict_to_str
 from ..basic import _load_lib
 
-__all__ = ["gradients", "metric", "sample_rows", "forest_predict", "leaf_sums", "add_leaf_values",
+__all__ = ["gradients", "metric", "sample_rows", "forest_predict", "tensor_predict_launch_info", "leaf_sums", "add_leaf_values",
            "refit_launch_info", "csc_launch_info", "csr_group_bins", "csr_bin_launch_info",
            "convert_scores", "cast_gradients", "custom_launch_info", "sample_distinct", "bin_find_launch_info"]
 
@@ -263,6 +263,17 @@ def forest_predict(booster, X, kind="raw", start_iteration=0, num_iteration=-1):
                                        ctypes.c_int(start), ctypes.c_int(num), _dev_ptr(out, torch.float64, "out"),
                                        ctypes.c_int64(out.numel())))
     return out
+
+
+def tensor_predict_launch_info():
+    """The launch shape of ``Booster.predict_device`` (src/device/tensor_predict.h): ``ladder`` (the
+    rows a workgroup's tile may hold, tallest first), ``lds_bytes`` (what a tile may take; the plan
+    picks the first step whose tile fits, ``LGBM_AMD_TensorPredictPlan``) and ``max_leaves`` (the
+    most leaves of a tree whose nodes are packed; beyond them the slots route predicts)."""
+    out = (ctypes.c_int64 * 8)()
+    _native_call("LGBM_AMD_TensorPredictLaunchInfo", out)
+    n = out[0]
+    return {"ladder": list(out[1:1 + n]), "lds_bytes": out[1 + n], "max_leaves": out[2 + n]}
 
 
 def refit_launch_info():

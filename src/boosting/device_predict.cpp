@@ -119,6 +119,27 @@ class DeviceForest {
     }
     return true;
   }
+  int MaxLeaves() const { return flat_.MaxLeaves(); }
+  // after Upload with slots: the packed nodes and the slots' columns, and what k_predict_tile
+  // reads of the forest into `a`
+  void UploadPacked(dev::TensorPredictArgs* a, hipStream_t s) {
+    packed_.Build(flat_, slots_);
+    a->nodes = b_.Upload(packed_.nodes, s);
+    a->used = b_.Upload(slots_.used, s);
+    a->num_slots = NumSlots();
+    a->num_trees = f_.num_trees;
+    a->num_class = f_.num_class;
+    a->node_off = f_.node_off;
+    a->leaf_off = f_.leaf_off;
+    a->leaf_value = f_.leaf_value;
+    a->cat_bits = f_.cat_bits;
+  }
+  // ... or the slots' columns alone, for the gather into the compact matrix
+  void UploadUsed(dev::TensorPredictArgs* a, hipStream_t s) {
+    a->used = b_.Upload(slots_.used, s);
+    a->num_slots = NumSlots();
+    a->num_class = f_.num_class;
+  }
   int NumSlots() const { return static_cast<int>(slots_.used.size()); }
   const int32_t* SlotOf() const { return slot_of_; }
   // the sorted features of the slots
@@ -171,6 +192,7 @@ class DeviceForest {
   FlatForest flat_;
   ShapPathTables paths_;
   FeatureSlots slots_;
+  PackedForest packed_;
   const int32_t* slot_of_ = nullptr;
   DeviceBuffers b_;
   dev::ForestArgs f_{};
@@ -484,6 +506,216 @@ void GBDT::PredictDeviceBuffers(const void* d_data, bool is_double, int64_t nrow
   if (nrow > 0) forest.Run(d_data, is_double, true, nrow, ncol, d_out, nullptr);
   HIPCHECK(hipStreamSynchronize(nullptr));
   ++g_device_predictions;
+}
+
+namespace {
+
+// the caller's device again when the scope ends
+struct DeviceGuard {
+  int prev = -1;
+  explicit DeviceGuard(int dev) {
+    HIPCHECK(hipGetDevice(&prev));
+    HIPCHECK(hipSetDevice(dev));
+  }
+  ~DeviceGuard() {
+    if (prev >= 0) (void)hipSetDevice(prev);
+  }
+};
+
+int PredictTypeOf(DevicePredictKind kind) {
+  switch (kind) {
+    case DevicePredictKind::Normal: return 0;
+    case DevicePredictKind::Raw: return 1;
+    case DevicePredictKind::Leaf: return 2;
+    default: return 3;
+  }
+}
+
+size_t TensorElementBytes(int data_type) {
+  size_t bytes = 0;
+  if (!dev::DispatchTensorElement(data_type, [&](auto* p) { bytes = sizeof(*p); })) {
+    Log::Fatal("Unknown data type of a device matrix: %d", data_type);
+  }
+  return bytes;
+}
+
+}  // namespace
+
+template <typename Args>
+void GBDT::TensorPredictChecks(const void* data, int64_t nrow, int ncol, int64_t row_stride, int64_t col_stride,
+                               DevicePredictKind kind, Args* a) {
+  if (data == nullptr || nrow <= 0 || ncol <= 0) {
+    Log::Fatal("device matrix: null pointer or %lld x %d", static_cast<long long>(nrow), ncol);
+  }
+  if (row_stride < 0 || col_stride < 0) Log::Fatal("device matrix: negative stride");
+  if (ncol != max_feature_idx_ + 1) {
+    Log::Fatal("The number of features in data (%d) is not the same as it was in training data (%d).", ncol,
+               max_feature_idx_ + 1);
+  }
+  if (num_tree_per_iteration_ > dev::kMaxPredClasses) {
+    Log::Fatal("forest prediction on the device handles at most %d trees per iteration", dev::kMaxPredClasses);
+  }
+  // (after InitPredict: the window's iterations divide the scores of boosting=rf)
+  a->divisor = 0.0;
+  a->conv_kind = -1;
+  a->conv_param = 0.0;
+  if (kind == DevicePredictKind::Normal) {
+    if (average_output_) a->divisor = num_iteration_for_pred_;
+    if (objective_ != nullptr) {
+      a->conv_kind = objective_->DeviceOutputKind(&a->conv_param);
+      if (a->conv_kind < 0) Log::Fatal("the objective's output transform has no device form: predict raw scores");
+    }
+  }
+  a->row_stride = row_stride;
+  a->col_stride = col_stride;
+  a->leaf = kind == DevicePredictKind::Leaf ? 1 : 0;
+}
+
+void GBDT::PredictDeviceTensor(const void* d_data, int data_type, int64_t nrow, int ncol, int64_t row_stride,
+                               int64_t col_stride, int device_id, DevicePredictKind kind, int start_iteration,
+                               int num_iteration, double* d_out, int64_t out_len) {
+  const size_t elem = TensorElementBytes(data_type);
+  const std::vector<const Tree*> trees = PredictWindowTrees(start_iteration, num_iteration);
+  dev::TensorPredictArgs a{};
+  tuning::PoisonArgs(&a);  // (every field that a launch reads is set below)
+  TensorPredictChecks(d_data, nrow, ncol, row_stride, col_stride, kind, &a);
+  a.data = d_data;
+  a.data_type = data_type;
+  a.num_rows = nrow;
+  a.out = d_out;
+  const DeviceGuard guard(device_id);
+  DeviceForest forest;
+  if (!forest.Upload(trees, num_tree_per_iteration_, max_feature_idx_ + 1, kind, nullptr, true)) {
+    Log::Fatal("contributions on the device need paths of at most %d distinct features and data counts on every node",
+               dev::kShapMaxPathLen - 1);
+  }
+  const int64_t per_out = forest.OutPerRow();
+  if (out_len != nrow * per_out) {
+    Log::Fatal("output holds %lld doubles, the prediction has %lld", static_cast<long long>(out_len),
+               static_cast<long long>(nrow * per_out));
+  }
+  dev::TensorPredictPlan plan =
+      dev::PlanTensorPredict(forest.NumSlots(), static_cast<int>(elem), forest.MaxLeaves(), PredictTypeOf(kind));
+  if (tuning::On(tuning::Knob::TensorPredictSlots)) plan.route = dev::kTensorRouteSlots;
+  if (plan.route == dev::kTensorRouteTile) {
+    forest.UploadPacked(&a, nullptr);
+    a.tile_rows = plan.rows;
+    dev::PredictTensorTile(a, nullptr);
+    HIPCHECK(hipGetLastError());
+  } else {
+    // the compact matrix of a chunk of rows, then the forest kernels of the sparse paths on it
+    forest.UploadUsed(&a, nullptr);
+    const int ns = forest.NumSlots();
+    const size_t out_elem = elem == 8 ? 8 : 4;
+    size_t free_b = 0, total_b = 0;
+    HIPCHECK(hipMemGetInfo(&free_b, &total_b));
+    PredictChunkPlan chunks = PlanPredictChunks(
+        nrow, free_b - free_b / 5, forest.ScratchBytes(nrow), std::max<size_t>(1, static_cast<size_t>(ns) * out_elem), 0,
+        tuning::Int(tuning::Knob::PredictChunkRows, 0), dev::kShapLanes, [](int64_t) { return int64_t{0}; });
+    if (!chunks.fits) Log::Fatal("device matrix: not even %d rows of %d slots fit the free device memory", dev::kShapLanes, ns);
+    // (a launch of the gather: row tiles x slot batches of at least 8 slots in one grid dimension)
+    const int64_t most = int64_t{0x7fffffff} / (ns / 8 + 1) * 256;
+    chunks.chunk = std::min(chunks.chunk, most);
+    DeviceBuffers b;
+    void* d_mat = b.Alloc(static_cast<size_t>(chunks.chunk) * ns * out_elem);
+    for (int64_t r0 = 0; r0 < nrow; r0 += chunks.chunk) {
+      a.num_rows = std::min(chunks.chunk, nrow - r0);
+      a.data = static_cast<const char*>(d_data) + static_cast<size_t>(r0) * row_stride * elem;
+      a.out = d_out + r0 * per_out;
+      dev::TensorToSlots(a, d_mat, nullptr);
+      HIPCHECK(hipGetLastError());
+      forest.Run(d_mat, out_elem == 8, false, a.num_rows, ns, a.out, nullptr);
+      if (a.divisor > 0.0 || a.conv_kind > 0) {
+        dev::ConvertTensorScores(a, nullptr);
+        HIPCHECK(hipGetLastError());
+      }
+    }
+  }
+  HIPCHECK(hipStreamSynchronize(nullptr));
+  ++g_device_predictions;
+}
+
+void GBDT::TensorPredictOnHost(const void* data, int data_type, int64_t nrow, int ncol, int64_t row_stride,
+                               int64_t col_stride, DevicePredictKind kind, int start_iteration, int num_iteration,
+                               double* out, int64_t out_len) {
+  const size_t elem = TensorElementBytes(data_type);
+  if (kind == DevicePredictKind::Contrib) Log::Fatal("contributions are not evaluated on the host by this entry");
+  const std::vector<const Tree*> trees = PredictWindowTrees(start_iteration, num_iteration);
+  dev::TensorPredictArgs a{};
+  TensorPredictChecks(data, nrow, ncol, row_stride, col_stride, kind, &a);
+  FlatForest flat;
+  flat.Build(trees);
+  FeatureSlots slots;
+  slots.Build(flat, max_feature_idx_ + 1);
+  const int ns = static_cast<int>(slots.used.size());
+  const int nt = static_cast<int>(trees.size()), nc = num_tree_per_iteration_;
+  const int64_t per_out = a.leaf ? nt : nc;
+  if (out_len != nrow * per_out) {
+    Log::Fatal("output holds %lld doubles, the prediction has %lld", static_cast<long long>(out_len),
+               static_cast<long long>(nrow * per_out));
+  }
+  dev::TensorPredictPlan plan = dev::PlanTensorPredict(ns, static_cast<int>(elem), flat.MaxLeaves(), PredictTypeOf(kind));
+  if (tuning::On(tuning::Knob::TensorPredictSlots)) plan.route = dev::kTensorRouteSlots;
+  // one row's trees, in model order, from leaf_of(tree)
+  auto row_out = [&](int64_t r, auto&& leaf_of) {
+    double score[dev::kMaxPredClasses] = {};
+    for (int t = 0; t < nt; ++t) {
+      const int leaf = leaf_of(t);
+      if (a.leaf) out[r * nt + t] = leaf;
+      else score[t % nc] += flat.leaf_value[flat.leaf_off[t] + leaf];
+    }
+    if (a.leaf) return;
+    dev::FinishScoreRow(score, nc, a.divisor, a.conv_kind, a.conv_param);
+    std::copy(score, score + nc, out + r * nc);
+  };
+  dev::DispatchTensorElement(data_type, [&](auto* p) {
+    using T = std::remove_cv_t<std::remove_pointer_t<decltype(p)>>;
+    const T* x = static_cast<const T*>(data);
+    if (plan.route == dev::kTensorRouteTile) {
+      PackedForest packed;
+      packed.Build(flat, slots);
+      const int R = plan.rows, pitch = dev::TensorTilePitch(R, static_cast<int>(sizeof(T)));
+      std::vector<T> tile(static_cast<size_t>(dev::TensorTileBytes(ns, R, static_cast<int>(sizeof(T))) / sizeof(T)));
+      for (int64_t row0 = 0; row0 < nrow; row0 += R) {
+        const int nr = static_cast<int>(std::min<int64_t>(R, nrow - row0));
+        for (int c = 0; c < ns; ++c) {
+          for (int r = 0; r < nr; ++r) tile[c * pitch + r] = x[row_stride * (row0 + r) + col_stride * slots.used[c]];
+        }
+        for (int r = 0; r < nr; ++r) {
+          row_out(row0 + r, [&](int t) {
+            const int n0 = flat.node_off[t];
+            return dev::PackedTreeLeaf(packed.nodes.data() + n0, flat.node_off[t + 1] - n0, flat.cat_bits.data(),
+                                       tile.data() + r, pitch);
+          });
+        }
+      }
+    } else {
+      // the compact matrix as the gather writes it, walked as the forest kernels walk it
+      using O = std::conditional_t<std::is_same<T, double>::value, double, float>;
+      std::vector<O> mat(static_cast<size_t>(ns) * nrow);
+      for (int c = 0; c < ns; ++c) {
+        for (int64_t r = 0; r < nrow; ++r) {
+          mat[c * nrow + r] = static_cast<O>(dev::WidenElement(x[row_stride * r + col_stride * slots.used[c]]));
+        }
+      }
+      dev::ForestArgs f{};
+      flat.HostArgs(&f);
+      f.feature = slots.feature.data();
+      for (int64_t r = 0; r < nrow; ++r) {
+        row_out(r, [&](int t) {
+          const int n0 = flat.node_off[t];
+          if (flat.node_off[t + 1] <= n0) return 0;
+          int node = 0;
+          while (node >= 0) {
+            const int gi = n0 + node;
+            const double v = static_cast<double>(mat[static_cast<int64_t>(f.feature[gi]) * nrow + r]);
+            node = dev::ForestGoesLeft(f, t, gi, v) ? f.left[gi] : f.right[gi];
+          }
+          return ~node;
+        });
+      }
+    }
+  });
 }
 
 bool GBDT::PredictCSROnDevice(const void* indptr, bool indptr_is_64, const int32_t* indices, const void* data,

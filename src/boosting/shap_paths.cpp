@@ -51,6 +51,36 @@ void FlatForest::HostArgs(dev::ForestArgs* f) const {
   f->cat_bits = cat_bits.data();
 }
 
+int FlatForest::MaxLeaves() const {
+  int most = 0;
+  for (size_t t = 0; t < leaf_off.size(); ++t) {
+    const size_t end = t + 1 < leaf_off.size() ? static_cast<size_t>(leaf_off[t + 1]) : leaf_value.size();
+    most = std::max(most, static_cast<int>(end - leaf_off[t]));
+  }
+  return most;
+}
+
+void PackedForest::Build(const FlatForest& flat, const FeatureSlots& slots) {
+  if (flat.MaxLeaves() > dev::kPackedMaxLeaves) {
+    Log::Fatal("packed nodes: a tree of %d leaves, 16-bit children name %d", flat.MaxLeaves(), dev::kPackedMaxLeaves);
+  }
+  nodes.resize(flat.feature.size());
+  for (size_t t = 0; t + 1 < flat.node_off.size(); ++t) {
+    const int32_t* bound = flat.cat_bound.data() + flat.cat_bound_off[t];
+    for (int gi = flat.node_off[t]; gi < flat.node_off[t + 1]; ++gi) {
+      const int dt = flat.dtype[gi];
+      uint32_t bits_off = 0, bits_words = 0;
+      if (dt & 1) {
+        const int ci = static_cast<int>(flat.threshold[gi]);
+        bits_off = static_cast<uint32_t>(flat.cat_bits_off[t] + bound[ci]);
+        bits_words = static_cast<uint32_t>(bound[ci + 1] - bound[ci]);
+      }
+      nodes[gi] = dev::PackNode(dt, flat.threshold[gi], bits_off, bits_words, slots.feature[gi], flat.left[gi],
+                                flat.right[gi]);
+    }
+  }
+}
+
 void FeatureSlots::Build(const FlatForest& flat, int num_features) {
   slot_of.assign(std::max(0, num_features), -1);
   for (const int32_t f : flat.feature) {

@@ -14,6 +14,7 @@
 #include <vector>
 
 #include "../device/kernels.h"
+#include "../device/tensor_predict.h"
 #include "lgbm_amd/tree.h"
 
 namespace lgbm_amd {
@@ -27,6 +28,8 @@ struct FlatForest {
   void Build(const std::vector<const Tree*>& trees);
   // the forest fields of `f` pointing at these host vectors
   void HostArgs(dev::ForestArgs* f) const;
+  // the leaves of the largest tree
+  int MaxLeaves() const;
 };
 
 // The distinct features a forest splits on, for sparse rows (src/device/csr_slots.h): used[] is
@@ -37,6 +40,16 @@ struct FeatureSlots {
   std::vector<int32_t> used, slot_of, feature;
 
   void Build(const FlatForest& flat, int num_features);
+};
+
+// The internal nodes of a forest as one 16-byte record each (dev::PackedNode,
+// src/device/tensor_predict.h), in FlatForest's node order: the split feature as its slot, a
+// categorical node's bitset resolved to its words in FlatForest::cat_bits.  For trees of at most
+// dev::kPackedMaxLeaves leaves (FlatForest::MaxLeaves)
+struct PackedForest {
+  std::vector<dev::PackedNode> nodes;
+
+  void Build(const FlatForest& flat, const FeatureSlots& slots);
 };
 
 struct ShapPathTables {

@@ -41,6 +41,7 @@
 #include "../device/kernels.h"
 #include "../device/refit_quant.h"
 #include "../device/score_convert.h"
+#include "../device/tensor_predict.h"
 #include "../treelearner/growth_limits.h"
 #include "booster_device_buffers.h"
 
@@ -2014,6 +2015,54 @@ int LGBM_AMD_DeviceBinCscStats(int64_t* csc_calls, int64_t* column_samples) {
 int LGBM_AMD_DevicePredictCount(int64_t* out) {
   API_BEGIN();
   *out = GBDT::DevicePredictions();
+  API_END();
+}
+
+int LGBM_AMD_BoosterPredictForDeviceMat(BoosterHandle handle, const void* d_data, int data_type, int64_t nrow,
+                                        int32_t ncol, int64_t row_stride, int64_t col_stride, int device_id,
+                                        int predict_type, int start_iteration, int num_iteration, double* d_out,
+                                        int64_t out_len) {
+  API_BEGIN();
+  DevicePredictKind kind;
+  if (!Booster::DeviceKindOf(predict_type, &kind)) Log::Fatal("Unknown predict type %d", predict_type);
+  const auto booster_lock = WriteLock(handle);
+  static_cast<Booster*>(handle)->boosting()->PredictDeviceTensor(d_data, data_type, nrow, ncol, row_stride, col_stride,
+                                                                 device_id, kind, start_iteration, num_iteration, d_out,
+                                                                 out_len);
+  API_END();
+}
+
+int LGBM_AMD_TensorPredictOnHost(BoosterHandle handle, const void* data, int data_type, int64_t nrow, int32_t ncol,
+                                 int64_t row_stride, int64_t col_stride, int predict_type, int start_iteration,
+                                 int num_iteration, double* out, int64_t out_len) {
+  API_BEGIN();
+  DevicePredictKind kind;
+  if (!Booster::DeviceKindOf(predict_type, &kind)) Log::Fatal("Unknown predict type %d", predict_type);
+  const auto booster_lock = WriteLock(handle);
+  static_cast<Booster*>(handle)->boosting()->TensorPredictOnHost(data, data_type, nrow, ncol, row_stride, col_stride,
+                                                                 kind, start_iteration, num_iteration, out, out_len);
+  API_END();
+}
+
+int LGBM_AMD_TensorPredictPlan(int32_t num_slots, int32_t elem_size, int32_t max_leaves, int predict_type,
+                               int32_t* out) {
+  API_BEGIN();
+  if (num_slots < 0 || max_leaves < 1 || (elem_size != 2 && elem_size != 4 && elem_size != 8) || predict_type < 0 ||
+      predict_type > C_API_PREDICT_CONTRIB) {
+    Log::Fatal("TensorPredictPlan: need num_slots >= 0, elem_size 2, 4 or 8, max_leaves >= 1 and a predict type");
+  }
+  const dev::TensorPredictPlan plan = dev::PlanTensorPredict(num_slots, elem_size, max_leaves, predict_type);
+  out[0] = plan.route;
+  out[1] = plan.rows;
+  API_END();
+}
+
+int LGBM_AMD_TensorPredictLaunchInfo(int64_t* out) {
+  API_BEGIN();
+  out[0] = dev::kTensorPredictSteps;
+  for (int k = 0; k < dev::kTensorPredictSteps; ++k) out[1 + k] = dev::kTensorPredictLadder[k];
+  out[1 + dev::kTensorPredictSteps] = dev::kTensorPredictLdsBytes;
+  out[2 + dev::kTensorPredictSteps] = dev::kPackedMaxLeaves;
   API_END();
 }
 

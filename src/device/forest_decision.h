@@ -14,27 +14,39 @@
 namespace lgbm_amd {
 namespace dev {
 
-// true: the row goes to the left child of node `gi` (global node index) of tree `t`
-LGBM_AMD_HD bool ForestGoesLeft(const ForestArgs& f, int t, int gi, double v) {
+// The rule on a node's fields by value (the packed nodes of src/device/tensor_predict.h carry
+// them): decision type dt, the threshold of a numerical node, and the nw words at `bits` of a
+// categorical node's bitset (neither is read at a numerical node).  true: the row goes left
+LGBM_AMD_HD bool ForestGoesLeft(int dt, double threshold, const uint32_t* bits, int nw, double v) {
   constexpr double kZero = 1e-35f;  // kZeroThreshold
   if (fabs(v) <= kZero) v = 0.0;
-  const int8_t dt = f.dtype[gi];
   const int mt = (dt >> 2) & 3;
   if (dt & 1) {  // categorical
     // NaN goes right whatever the missing type, as in the host predictor (whose int cast of a NaN
     // is negative); the casts are kept in range so that host and device agree on every value
     if (v != v || !(v > -1.0)) return false;
     const int iv = v >= 2147483647.0 ? 2147483647 : static_cast<int>(v);
-    const int32_t* bound = f.cat_bound + f.cat_bound_off[t];
-    const uint32_t* bits = f.cat_bits + f.cat_bits_off[t];
-    const int ci = static_cast<int>(f.threshold[gi]);
-    const int lo = bound[ci], nw = bound[ci + 1] - lo;
     const int w = iv >> 5;
-    return w < nw && ((bits[lo + w] >> (iv & 31)) & 1u);
+    return w < nw && ((bits[w] >> (iv & 31)) & 1u);
   }
   if (v != v && mt != 2) v = 0.0;
   if ((mt == 1 && fabs(v) <= kZero) || (mt == 2 && v != v)) return (dt & 2) != 0;
-  return v <= f.threshold[gi];
+  return v <= threshold;
+}
+
+// true: the row goes to the left child of node `gi` (global node index) of tree `t`
+LGBM_AMD_HD bool ForestGoesLeft(const ForestArgs& f, int t, int gi, double v) {
+  const int8_t dt = f.dtype[gi];
+  const double threshold = f.threshold[gi];
+  const uint32_t* bits = nullptr;
+  int nw = 0;
+  if (dt & 1) {  // (the threshold of a categorical node indexes the tree's boundaries)
+    const int32_t* bound = f.cat_bound + f.cat_bound_off[t];
+    const int ci = static_cast<int>(threshold);
+    bits = f.cat_bits + f.cat_bits_off[t] + bound[ci];
+    nw = bound[ci + 1] - bound[ci];
+  }
+  return ForestGoesLeft(dt, threshold, bits, nw, v);
 }
 
 }  // namespace dev

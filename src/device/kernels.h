@@ -661,6 +661,40 @@ struct CscSlotsArgs {
 void CscColumnOrder(const CscSlotsArgs& c, hipStream_t s);
 void CscToSlots(const CscSlotsArgs& c, hipStream_t s);
 
+// prediction of a strided matrix in device memory (src/device/tensor_predict.h has the plan, the
+// tile, the packed node and the walk; src/device/tensor_predict_kernels.hip): element (r, c) at
+// data[r * row_stride + c * col_stride] of data_type (the C API's float32 / float64 / float16 /
+// bfloat16 codes)
+struct PackedNode;
+struct TensorPredictArgs {
+  const void* data{};
+  int32_t data_type{};
+  int32_t num_slots{};
+  int64_t row_stride{}, col_stride{};  // in elements, not negative
+  int64_t num_rows{};
+  const int32_t* used{};      // [num_slots] the column of each slot
+  // PredictTensorTile: the window's trees
+  int32_t tile_rows{};        // rows of a workgroup's tile (a step of kTensorPredictLadder)
+  int32_t num_trees{};
+  int32_t num_class{};        // trees per iteration (<= kMaxPredClasses)
+  int32_t leaf{};             // out: [num_rows][num_trees] leaf indices (else [num_rows][num_class] scores)
+  const PackedNode* nodes{};
+  const int32_t* node_off{};  // [num_trees + 1]
+  const int32_t* leaf_off{};  // [num_trees]
+  const double* leaf_value{};
+  const uint32_t* cat_bits{};
+  // the finish of a row of scores (FinishScoreRow; ConvertTensorScores applies it to `out` in place)
+  double divisor{};           // > 0: average_output
+  int32_t conv_kind{};        // ObjectiveFunction::DeviceOutputKind, -1: raw scores
+  double conv_param{};
+  double* out{};
+};
+void PredictTensorTile(const TensorPredictArgs& a, hipStream_t s);
+// rows [0, num_rows) into the compact column-major matrix [num_slots][num_rows] that the forest
+// kernels read: float64 elements as float64, the others as float32 (exact)
+void TensorToSlots(const TensorPredictArgs& a, void* d_mat, hipStream_t s);
+void ConvertTensorScores(const TensorPredictArgs& a, hipStream_t s);
+
 // validation metrics on device scores (one model per iteration)
 constexpr int kMetricL2 = 1, kMetricRMSE = 2, kMetricL1 = 3, kMetricBinLogloss = 4, kMetricBinError = 5,
               kMetricAUC = 6, kMetricQuantile = 7, kMetricHuber = 8, kMetricFair = 9, kMetricPoisson = 10,
