@@ -147,15 +147,18 @@ class GBDT {
   // Predict / PredictRaw / PredictLeafIndex / PredictContrib give them for the values as float64.
   // src/device/tensor_predict.h plans the route: the tile kernel, or the compact matrix of the
   // sparse paths in chunks of rows.  Runs on the device's null stream, restores the caller's device
-  // and returns when the data is complete; what is not applicable is an error
+  // and returns when the data is complete; what is not applicable is an error.  early_stop_freq > 0
+  // asks for pred_early_stop with that period and early_stop_margin (src/device/tensor_predict.h
+  // states the rule and where it applies; elsewhere it is ignored, as by the host predictor)
   void PredictDeviceTensor(const void* d_data, int data_type, int64_t nrow, int ncol, int64_t row_stride,
                            int64_t col_stride, int device_id, DevicePredictKind kind, int start_iteration,
-                           int num_iteration, double* d_out, int64_t out_len);
+                           int num_iteration, double* d_out, int64_t out_len, int early_stop_freq = 0,
+                           double early_stop_margin = 0.0);
   // the same plan, tile and packed-node walk evaluated on a host matrix of that description
   // (tests; needs no device): Normal, Raw or Leaf into out_len doubles
   void TensorPredictOnHost(const void* data, int data_type, int64_t nrow, int ncol, int64_t row_stride,
                            int64_t col_stride, DevicePredictKind kind, int start_iteration, int num_iteration,
-                           double* out, int64_t out_len);
+                           double* out, int64_t out_len, int early_stop_freq = 0, double early_stop_margin = 0.0);
   // the same predictions of the rows of a host CSR matrix (indptr int32 / int64, nindptr = rows +
   // 1 entries): each chunk of rows is scattered on the device into a compact matrix of the
   // features the window's trees split on, which the same kernels walk.  Absent entries are 0,
@@ -329,10 +332,10 @@ class GBDT {
                               int start_iteration, int num_iteration);
   // ... and PredictDeviceTensor / TensorPredictOnHost, after InitPredict: the checks of the matrix,
   // the column and class counts, and into `a` (dev::TensorPredictArgs) the strides, the kind and
-  // what the host predictor does to a row of raw scores
+  // what the host predictor does to a row of raw scores, early stopping included where it applies
   template <typename Args>
   void TensorPredictChecks(const void* data, int64_t nrow, int ncol, int64_t row_stride, int64_t col_stride,
-                           DevicePredictKind kind, Args* a);
+                           DevicePredictKind kind, int early_stop_freq, double early_stop_margin, Args* a);
   int num_init_iteration_ = 0;
   std::vector<std::string> feature_names_;
   std::vector<std::string> feature_infos_;

@@ -428,6 +428,27 @@ LIGHTGBM_C_EXPORT int LGBM_AMD_TensorPredictOnHost(BoosterHandle handle, const v
 // sparse paths) and out[1] the rows of a tile
 LIGHTGBM_C_EXPORT int LGBM_AMD_TensorPredictPlan(int32_t num_slots, int32_t elem_size, int32_t max_leaves,
                                                  int predict_type, int32_t* out);
+// Early-stopped predictions (the pred_early_stop / pred_early_stop_freq / pred_early_stop_margin
+// parameters) of the same matrices: where the host predictor would stop rows early -- normal and raw
+// scores of a booster whose objective does not need an accurate prediction -- a row's scores are
+// those after the first pred_early_stop_freq-th iteration of the window at which its margin (2 |score|
+// of a binary booster, else the largest minus the second largest class score) is above
+// pred_early_stop_margin, then transformed as usual; elsewhere the option is ignored.  There,
+// pred_early_stop_freq <= 0 or pred_early_stop_margin < 0 is an error.  pred_early_stop = 0 is the
+// entry above
+LIGHTGBM_C_EXPORT int LGBM_AMD_BoosterPredictForDeviceMatEarlyStop(
+    BoosterHandle handle, const void* d_data, int data_type, int64_t nrow, int32_t ncol, int64_t row_stride,
+    int64_t col_stride, int device_id, int predict_type, int start_iteration, int num_iteration, int pred_early_stop,
+    int pred_early_stop_freq, double pred_early_stop_margin, double* d_out, int64_t out_len);
+// ... evaluated on the host (no GPU), over the tile or the compact matrix as the kernels walk them
+LIGHTGBM_C_EXPORT int LGBM_AMD_TensorPredictOnHostEarlyStop(
+    BoosterHandle handle, const void* data, int data_type, int64_t nrow, int32_t ncol, int64_t row_stride,
+    int64_t col_stride, int predict_type, int start_iteration, int num_iteration, int pred_early_stop,
+    int pred_early_stop_freq, double pred_early_stop_margin, double* out, int64_t out_len);
+// ... and their plan: LGBM_AMD_TensorPredictPlan with the LDS bytes that the period end of a
+// workgroup takes for num_class trees per iteration taken off the tile's budget; out[2]: those bytes
+LIGHTGBM_C_EXPORT int LGBM_AMD_TensorPredictStopPlan(int32_t num_slots, int32_t elem_size, int32_t max_leaves,
+                                                     int predict_type, int32_t num_class, int32_t* out);
 // its launch shape (tests place shapes on the boundaries; out has room for 8 values): out[0] = n the
 // steps of the ladder of tile heights, out[1..n] the heights, tallest first, out[n + 1] the LDS
 // bytes a tile may take, out[n + 2] the most leaves of a tree whose nodes are packed

@@ -80,6 +80,7 @@ constexpr int kQueryMetricDeviceMaxDocs = 16384;
   X(TextBlockBytes, "LGBM_AMD_TEXT_BLOCK_BYTES", "n: text reader block size (tests)")                          \
   X(PredictChunkRows, "LGBM_AMD_PREDICT_CHUNK_ROWS", "n: rows per chunk of a device prediction (tests; auto from free memory)")  \
   X(TensorPredictSlots, "LGBM_AMD_TENSOR_PREDICT_SLOTS", "1: the prediction of a GPU tensor takes the slots route whatever the plan says (A/B, tests; same results)")  \
+  X(TensorStopCompact, "LGBM_AMD_TENSOR_STOP_COMPACT", "0: the early-stopped prediction of a GPU tensor leaves surviving rows on their lanes (A/B; same results)")  \
   X(BinChunkRows, "LGBM_AMD_BIN_CHUNK_ROWS", "n: rows per chunk of the device binning of a CSR matrix (tests; auto: 256 MiB of entries / of bins)")  \
   X(BinChunkGroups, "LGBM_AMD_BIN_CHUNK_GROUPS", "n: feature groups per window of the device binning of a CSC matrix (tests; auto: 256 MiB of bins and entries)")  \
   X(CscColumnSample, "LGBM_AMD_CSC_COLUMN_SAMPLE", "1: the host CSC construction takes its bin sample column by column, as the device path does (tests, A/B; same dataset)")  \

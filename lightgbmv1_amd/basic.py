@@ -1339,13 +1339,17 @@ class Booster:
             data, start_iteration, num_iteration, raw_score, pred_leaf, pred_contrib, data_has_header, is_reshape)
 
     def predict_device(self, data, start_iteration=0, num_iteration=None, raw_score=False, pred_leaf=False,
-                       pred_contrib=False):
+                       pred_contrib=False, pred_early_stop=False, pred_early_stop_freq=10,
+                       pred_early_stop_margin=10.0):
         """Predictions for the rows of a GPU tensor, computed where it lies and left there: ``data`` is
         a non-empty 2-D float16, bfloat16, float32 or float64 torch tensor on a GPU with any
         non-negative strides; the result is a float64 tensor ``[n, width]`` on the same device, with
         the values and widths of :meth:`predict` (scores go through the objective's output
         transform on the device unless ``raw_score``).  Any booster and any number of rows; neither
-        rows nor results pass through the host (src/device/tensor_predict_kernels.hip)."""
+        rows nor results pass through the host (src/device/tensor_predict_kernels.hip).
+        ``pred_early_stop`` with its two parameters stops the rows of a classification or ranking
+        booster early, at the iterations and with the scores of :meth:`predict` under the same
+        parameters; for other boosters and outputs it is ignored."""
         import torch
         if not (_is_gpu_tensor(data) and data.dim() == 2 and str(data.dtype) in _DEVICE_MAT_CODES
                 and data.numel() > 0):
@@ -1362,11 +1366,13 @@ class Booster:
                  nat.c_int(num_iteration), ctypes.byref(width))
         out = torch.empty((n, width.value), dtype=torch.float64, device=t.device)
         torch.cuda.synchronize(t.device)  # (the caller's writes of the tensor; the library uses the null stream)
-        nat.call("LGBM_AMD_BoosterPredictForDeviceMat", self.handle, ctypes.c_void_p(t.data_ptr()),
+        nat.call("LGBM_AMD_BoosterPredictForDeviceMatEarlyStop", self.handle, ctypes.c_void_p(t.data_ptr()),
                  nat.c_int(_DEVICE_MAT_CODES[str(t.dtype)]), ctypes.c_int64(n), ctypes.c_int32(t.shape[1]),
                  ctypes.c_int64(t.stride(0)), ctypes.c_int64(t.stride(1)), nat.c_int(t.device.index),
                  nat.c_int(ptype), nat.c_int(start_iteration), nat.c_int(num_iteration),
-                 ctypes.c_void_p(out.data_ptr()), ctypes.c_int64(out.numel()))
+                 nat.c_int(1 if pred_early_stop else 0), nat.c_int(pred_early_stop_freq),
+                 ctypes.c_double(pred_early_stop_margin), ctypes.c_void_p(out.data_ptr()),
+                 ctypes.c_int64(out.numel()))
         return out
 
     def refit(self, data, label, decay_rate=0.9, **kwargs):

@@ -186,6 +186,20 @@ class DeviceForest {
     }
     HIPCHECK(hipGetLastError());
   }
+  // early-stopped, finished scores of the compact column-major matrix d_data (`a`: the period, the
+  // margin, the finish and the output)
+  void RunStop(const void* d_data, bool is_double, int64_t rows, int ncol, const dev::TensorPredictArgs& a,
+               hipStream_t s) {
+    dev::ForestArgs f = f_;
+    f.num_cols = ncol;
+    f.is_double = is_double ? 1 : 0;
+    f.row_major = 0;
+    f.num_rows = rows;
+    f.data = d_data;
+    f.out = a.out;
+    dev::PredictForestStop(f, a, s);
+    HIPCHECK(hipGetLastError());
+  }
 
  private:
   DevicePredictKind kind_ = DevicePredictKind::Raw;
@@ -531,6 +545,17 @@ int PredictTypeOf(DevicePredictKind kind) {
   }
 }
 
+// the route of a prediction whose early stopping, if any, is in `a`
+dev::TensorPredictPlan PlanOf(const dev::TensorPredictArgs& a, int num_slots, size_t elem, int max_leaves,
+                              DevicePredictKind kind, int num_class) {
+  dev::TensorPredictPlan plan =
+      a.stop_freq > 0
+          ? dev::PlanTensorPredictStop(num_slots, static_cast<int>(elem), max_leaves, PredictTypeOf(kind), num_class)
+          : dev::PlanTensorPredict(num_slots, static_cast<int>(elem), max_leaves, PredictTypeOf(kind));
+  if (tuning::On(tuning::Knob::TensorPredictSlots)) plan.route = dev::kTensorRouteSlots;
+  return plan;
+}
+
 size_t TensorElementBytes(int data_type) {
   size_t bytes = 0;
   if (!dev::DispatchTensorElement(data_type, [&](auto* p) { bytes = sizeof(*p); })) {
@@ -543,7 +568,7 @@ size_t TensorElementBytes(int data_type) {
 
 template <typename Args>
 void GBDT::TensorPredictChecks(const void* data, int64_t nrow, int ncol, int64_t row_stride, int64_t col_stride,
-                               DevicePredictKind kind, Args* a) {
+                               DevicePredictKind kind, int early_stop_freq, double early_stop_margin, Args* a) {
   if (data == nullptr || nrow <= 0 || ncol <= 0) {
     Log::Fatal("device matrix: null pointer or %lld x %d", static_cast<long long>(nrow), ncol);
   }
@@ -569,16 +594,32 @@ void GBDT::TensorPredictChecks(const void* data, int64_t nrow, int ncol, int64_t
   a->row_stride = row_stride;
   a->col_stride = col_stride;
   a->leaf = kind == DevicePredictKind::Leaf ? 1 : 0;
+  // pred_early_stop where the host's Predictor applies it (src/device/tensor_predict.h)
+  a->stop_freq = 0;
+  a->stop_binary = 0;
+  a->stop_compact = tuning::Off(tuning::Knob::TensorStopCompact) ? 0 : 1;
+  a->stop_margin = 0.0;
+  const bool scores = kind == DevicePredictKind::Normal || kind == DevicePredictKind::Raw;
+  if (early_stop_freq > 0 && scores && !NeedAccuratePrediction()) {
+    LGBM_CHECK_GE(early_stop_margin, 0);
+    a->stop_freq = early_stop_freq;
+    a->stop_binary = NumberOfClasses() == 1 ? 1 : 0;
+    a->stop_margin = early_stop_margin;
+    if ((a->stop_binary != 0) != (num_tree_per_iteration_ == 1)) {
+      Log::Fatal("early stopping needs one tree per iteration of a binary booster and two or more otherwise");
+    }
+  }
 }
 
 void GBDT::PredictDeviceTensor(const void* d_data, int data_type, int64_t nrow, int ncol, int64_t row_stride,
                                int64_t col_stride, int device_id, DevicePredictKind kind, int start_iteration,
-                               int num_iteration, double* d_out, int64_t out_len) {
+                               int num_iteration, double* d_out, int64_t out_len, int early_stop_freq,
+                               double early_stop_margin) {
   const size_t elem = TensorElementBytes(data_type);
   const std::vector<const Tree*> trees = PredictWindowTrees(start_iteration, num_iteration);
   dev::TensorPredictArgs a{};
   tuning::PoisonArgs(&a);  // (every field that a launch reads is set below)
-  TensorPredictChecks(d_data, nrow, ncol, row_stride, col_stride, kind, &a);
+  TensorPredictChecks(d_data, nrow, ncol, row_stride, col_stride, kind, early_stop_freq, early_stop_margin, &a);
   a.data = d_data;
   a.data_type = data_type;
   a.num_rows = nrow;
@@ -594,9 +635,7 @@ void GBDT::PredictDeviceTensor(const void* d_data, int data_type, int64_t nrow, 
     Log::Fatal("output holds %lld doubles, the prediction has %lld", static_cast<long long>(out_len),
                static_cast<long long>(nrow * per_out));
   }
-  dev::TensorPredictPlan plan =
-      dev::PlanTensorPredict(forest.NumSlots(), static_cast<int>(elem), forest.MaxLeaves(), PredictTypeOf(kind));
-  if (tuning::On(tuning::Knob::TensorPredictSlots)) plan.route = dev::kTensorRouteSlots;
+  dev::TensorPredictPlan plan = PlanOf(a, forest.NumSlots(), elem, forest.MaxLeaves(), kind, num_tree_per_iteration_);
   if (plan.route == dev::kTensorRouteTile) {
     forest.UploadPacked(&a, nullptr);
     a.tile_rows = plan.rows;
@@ -624,6 +663,10 @@ void GBDT::PredictDeviceTensor(const void* d_data, int data_type, int64_t nrow, 
       a.out = d_out + r0 * per_out;
       dev::TensorToSlots(a, d_mat, nullptr);
       HIPCHECK(hipGetLastError());
+      if (a.stop_freq > 0) {
+        forest.RunStop(d_mat, out_elem == 8, a.num_rows, ns, a, nullptr);  // (finished where a row stops)
+        continue;
+      }
       forest.Run(d_mat, out_elem == 8, false, a.num_rows, ns, a.out, nullptr);
       if (a.divisor > 0.0 || a.conv_kind > 0) {
         dev::ConvertTensorScores(a, nullptr);
@@ -637,12 +680,12 @@ void GBDT::PredictDeviceTensor(const void* d_data, int data_type, int64_t nrow, 
 
 void GBDT::TensorPredictOnHost(const void* data, int data_type, int64_t nrow, int ncol, int64_t row_stride,
                                int64_t col_stride, DevicePredictKind kind, int start_iteration, int num_iteration,
-                               double* out, int64_t out_len) {
+                               double* out, int64_t out_len, int early_stop_freq, double early_stop_margin) {
   const size_t elem = TensorElementBytes(data_type);
   if (kind == DevicePredictKind::Contrib) Log::Fatal("contributions are not evaluated on the host by this entry");
   const std::vector<const Tree*> trees = PredictWindowTrees(start_iteration, num_iteration);
   dev::TensorPredictArgs a{};
-  TensorPredictChecks(data, nrow, ncol, row_stride, col_stride, kind, &a);
+  TensorPredictChecks(data, nrow, ncol, row_stride, col_stride, kind, early_stop_freq, early_stop_margin, &a);
   FlatForest flat;
   flat.Build(trees);
   FeatureSlots slots;
@@ -654,15 +697,19 @@ void GBDT::TensorPredictOnHost(const void* data, int data_type, int64_t nrow, in
     Log::Fatal("output holds %lld doubles, the prediction has %lld", static_cast<long long>(out_len),
                static_cast<long long>(nrow * per_out));
   }
-  dev::TensorPredictPlan plan = dev::PlanTensorPredict(ns, static_cast<int>(elem), flat.MaxLeaves(), PredictTypeOf(kind));
-  if (tuning::On(tuning::Knob::TensorPredictSlots)) plan.route = dev::kTensorRouteSlots;
-  // one row's trees, in model order, from leaf_of(tree)
+  const dev::TensorPredictPlan plan = PlanOf(a, ns, elem, flat.MaxLeaves(), kind, nc);
+  // one row's trees, in model order, from leaf_of(tree); with early stopping, up to the check
+  // (every stop_freq-th iteration of the window, whole) at which the row's margin is above the threshold
   auto row_out = [&](int64_t r, auto&& leaf_of) {
     double score[dev::kMaxPredClasses] = {};
-    for (int t = 0; t < nt; ++t) {
+    for (int t = 0, counter = 0; t < nt; ++t) {
       const int leaf = leaf_of(t);
       if (a.leaf) out[r * nt + t] = leaf;
       else score[t % nc] += flat.leaf_value[flat.leaf_off[t] + leaf];
+      if (a.stop_freq > 0 && (t + 1) % nc == 0 && ++counter == a.stop_freq) {
+        if (dev::StopMargin(score, nc, a.stop_binary != 0) > a.stop_margin) break;
+        counter = 0;
+      }
     }
     if (a.leaf) return;
     dev::FinishScoreRow(score, nc, a.divisor, a.conv_kind, a.conv_param);

@@ -2018,30 +2018,65 @@ int LGBM_AMD_DevicePredictCount(int64_t* out) {
   API_END();
 }
 
-int LGBM_AMD_BoosterPredictForDeviceMat(BoosterHandle handle, const void* d_data, int data_type, int64_t nrow,
-                                        int32_t ncol, int64_t row_stride, int64_t col_stride, int device_id,
-                                        int predict_type, int start_iteration, int num_iteration, double* d_out,
-                                        int64_t out_len) {
+namespace {
+
+// pred_early_stop as GBDT::PredictDeviceTensor takes it: the period, or 0 for none.  The checks are
+// the Predictor's (include/lgbm_amd/predictor.h): made whenever the booster could stop early
+int EarlyStopFreq(const GBDT* boosting, int pred_early_stop, int freq, double margin) {
+  if (pred_early_stop == 0 || boosting->NeedAccuratePrediction()) return 0;
+  LGBM_CHECK_GT(freq, 0);
+  LGBM_CHECK_GE(margin, 0);
+  return freq;
+}
+
+}  // namespace
+
+int LGBM_AMD_BoosterPredictForDeviceMatEarlyStop(BoosterHandle handle, const void* d_data, int data_type, int64_t nrow,
+                                                 int32_t ncol, int64_t row_stride, int64_t col_stride, int device_id,
+                                                 int predict_type, int start_iteration, int num_iteration,
+                                                 int pred_early_stop, int pred_early_stop_freq,
+                                                 double pred_early_stop_margin, double* d_out, int64_t out_len) {
   API_BEGIN();
   DevicePredictKind kind;
   if (!Booster::DeviceKindOf(predict_type, &kind)) Log::Fatal("Unknown predict type %d", predict_type);
   const auto booster_lock = WriteLock(handle);
-  static_cast<Booster*>(handle)->boosting()->PredictDeviceTensor(d_data, data_type, nrow, ncol, row_stride, col_stride,
-                                                                 device_id, kind, start_iteration, num_iteration, d_out,
-                                                                 out_len);
+  GBDT* boosting = static_cast<Booster*>(handle)->boosting();
+  const int freq = EarlyStopFreq(boosting, pred_early_stop, pred_early_stop_freq, pred_early_stop_margin);
+  boosting->PredictDeviceTensor(d_data, data_type, nrow, ncol, row_stride, col_stride, device_id, kind, start_iteration,
+                                num_iteration, d_out, out_len, freq, pred_early_stop_margin);
+  API_END();
+}
+
+int LGBM_AMD_BoosterPredictForDeviceMat(BoosterHandle handle, const void* d_data, int data_type, int64_t nrow,
+                                        int32_t ncol, int64_t row_stride, int64_t col_stride, int device_id,
+                                        int predict_type, int start_iteration, int num_iteration, double* d_out,
+                                        int64_t out_len) {
+  return LGBM_AMD_BoosterPredictForDeviceMatEarlyStop(handle, d_data, data_type, nrow, ncol, row_stride, col_stride,
+                                                      device_id, predict_type, start_iteration, num_iteration, 0, 0, 0.0,
+                                                      d_out, out_len);
+}
+
+int LGBM_AMD_TensorPredictOnHostEarlyStop(BoosterHandle handle, const void* data, int data_type, int64_t nrow,
+                                          int32_t ncol, int64_t row_stride, int64_t col_stride, int predict_type,
+                                          int start_iteration, int num_iteration, int pred_early_stop,
+                                          int pred_early_stop_freq, double pred_early_stop_margin, double* out,
+                                          int64_t out_len) {
+  API_BEGIN();
+  DevicePredictKind kind;
+  if (!Booster::DeviceKindOf(predict_type, &kind)) Log::Fatal("Unknown predict type %d", predict_type);
+  const auto booster_lock = WriteLock(handle);
+  GBDT* boosting = static_cast<Booster*>(handle)->boosting();
+  const int freq = EarlyStopFreq(boosting, pred_early_stop, pred_early_stop_freq, pred_early_stop_margin);
+  boosting->TensorPredictOnHost(data, data_type, nrow, ncol, row_stride, col_stride, kind, start_iteration,
+                                num_iteration, out, out_len, freq, pred_early_stop_margin);
   API_END();
 }
 
 int LGBM_AMD_TensorPredictOnHost(BoosterHandle handle, const void* data, int data_type, int64_t nrow, int32_t ncol,
                                  int64_t row_stride, int64_t col_stride, int predict_type, int start_iteration,
                                  int num_iteration, double* out, int64_t out_len) {
-  API_BEGIN();
-  DevicePredictKind kind;
-  if (!Booster::DeviceKindOf(predict_type, &kind)) Log::Fatal("Unknown predict type %d", predict_type);
-  const auto booster_lock = WriteLock(handle);
-  static_cast<Booster*>(handle)->boosting()->TensorPredictOnHost(data, data_type, nrow, ncol, row_stride, col_stride,
-                                                                 kind, start_iteration, num_iteration, out, out_len);
-  API_END();
+  return LGBM_AMD_TensorPredictOnHostEarlyStop(handle, data, data_type, nrow, ncol, row_stride, col_stride, predict_type,
+                                               start_iteration, num_iteration, 0, 0, 0.0, out, out_len);
 }
 
 int LGBM_AMD_TensorPredictPlan(int32_t num_slots, int32_t elem_size, int32_t max_leaves, int predict_type,
@@ -2054,6 +2089,21 @@ int LGBM_AMD_TensorPredictPlan(int32_t num_slots, int32_t elem_size, int32_t max
   const dev::TensorPredictPlan plan = dev::PlanTensorPredict(num_slots, elem_size, max_leaves, predict_type);
   out[0] = plan.route;
   out[1] = plan.rows;
+  API_END();
+}
+
+int LGBM_AMD_TensorPredictStopPlan(int32_t num_slots, int32_t elem_size, int32_t max_leaves, int predict_type,
+                                   int32_t num_class, int32_t* out) {
+  API_BEGIN();
+  if (num_slots < 0 || max_leaves < 1 || (elem_size != 2 && elem_size != 4 && elem_size != 8) || predict_type < 0 ||
+      predict_type > C_API_PREDICT_CONTRIB || num_class < 1 || num_class > dev::kMaxPredClasses) {
+    Log::Fatal("TensorPredictStopPlan: need num_slots >= 0, elem_size 2, 4 or 8, max_leaves >= 1, a predict type and "
+               "1 to %d classes", dev::kMaxPredClasses);
+  }
+  const dev::TensorPredictPlan plan = dev::PlanTensorPredictStop(num_slots, elem_size, max_leaves, predict_type, num_class);
+  out[0] = plan.route;
+  out[1] = plan.rows;
+  out[2] = dev::TensorStopLdsBytes(num_class);
   API_END();
 }
 

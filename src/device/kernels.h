@@ -687,13 +687,23 @@ struct TensorPredictArgs {
   double divisor{};           // > 0: average_output
   int32_t conv_kind{};        // ObjectiveFunction::DeviceOutputKind, -1: raw scores
   double conv_param{};
+  // early-stopped scores (the rule: src/device/tensor_predict.h; the stop kernels finish every row
+  // themselves, where it stops)
+  int32_t stop_freq{};        // iterations between two checks of a row's margin; 0: no early stop
+  int32_t stop_binary{};      // the margin is 2 |score| (else the largest sum minus the second largest)
+  int32_t stop_compact{};     // 0: surviving rows stay on their lanes (A/B); else they move to the lowest lanes
+  double stop_margin{};       // a row stops above it
   double* out{};
 };
+// scores and leaf indices of the tile route; with stop_freq > 0 the scores by k_predict_tile_stop
 void PredictTensorTile(const TensorPredictArgs& a, hipStream_t s);
 // rows [0, num_rows) into the compact column-major matrix [num_slots][num_rows] that the forest
 // kernels read: float64 elements as float64, the others as float32 (exact)
 void TensorToSlots(const TensorPredictArgs& a, void* d_mat, hipStream_t s);
 void ConvertTensorScores(const TensorPredictArgs& a, hipStream_t s);
+// early-stopped, finished scores of the slots route (a.stop_freq > 0): the forest `f` over its
+// compact column-major matrix, with the period, margin and finish of `a`
+void PredictForestStop(const ForestArgs& f, const TensorPredictArgs& a, hipStream_t s);
 
 // validation metrics on device scores (one model per iteration)
 constexpr int kMetricL2 = 1, kMetricRMSE = 2, kMetricL1 = 3, kMetricBinLogloss = 4, kMetricBinError = 5,

@@ -75,6 +75,58 @@ LGBM_AMD_HD TensorPredictPlan PlanTensorPredict(int num_slots, int elem_size, in
   return p;
 }
 
+// ---- early-stopped scores (pred_early_stop; reference src/boosting/prediction_early_stop.cpp and
+// GBDT::PredictRaw, src/boosting/gbdt_prediction.cpp:13-32; the host's Predictor).  The option applies
+// only to normal and raw scores of a booster whose objective does not need an accurate prediction
+// (binary, multiclass, multiclassova, the ranking objectives); everywhere else it is ignored
+// (GBDT::TensorStopRule decides).  A counter starts at the first iteration of the window; after every
+// freq-th iteration, with all of that iteration's trees added, a row whose StopMargin is above the
+// threshold (strictly) stops and keeps its sums, which FinishScoreRow then takes as they are.
+
+// the margin of a row of class sums: 2 |s| for a binary booster (NumberOfClasses() == 1), the
+// largest sum minus the second largest otherwise
+LGBM_AMD_HD double StopMargin(const double* score, int num_class, bool binary) {
+  if (binary) return 2.0 * __builtin_fabs(score[0]);
+  double top = score[0] > score[1] ? score[0] : score[1], second = score[0] > score[1] ? score[1] : score[0];
+  for (int k = 2; k < num_class; ++k) {
+    const double s = score[k];
+    if (s > top) {
+      second = top;
+      top = s;
+    } else if (s > second) {
+      second = s;
+    }
+  }
+  return top - second;
+}
+
+// LDS bytes that a workgroup of the stop kernels takes beside its tile (src/device/early_stop.h:
+// the period end): the moved rows' ids, a staging array of one class's sums -- one class at a
+// time, since all 16 classes of 256 rows at once would be 32 KiB of the tile's 52; two arrays in
+// turn when there are several classes, so that a class costs one barrier -- and the wave counts
+// of two periods in turn (3104 bytes for one class, 5152 for more)
+constexpr int kStopWaves = 4;  // waves of a workgroup of the stop kernels (256 rows)
+LGBM_AMD_HD int TensorStopLdsBytes(int num_class) {
+  const int rows = kTensorPredictLadder[0];
+  return rows * 4 + (num_class > 1 ? 2 : 1) * rows * 8 + 2 * kStopWaves * 4;
+}
+
+// the plan of an early-stopped prediction: the same ladder in what the period end leaves of the budget
+LGBM_AMD_HD TensorPredictPlan PlanTensorPredictStop(int num_slots, int elem_size, int max_leaves, int predict_type,
+                                                    int num_class) {
+  TensorPredictPlan p{kTensorRouteSlots, kTensorPredictLadder[0]};
+  if (predict_type == 3 || max_leaves > kPackedMaxLeaves) return p;
+  const int budget = kTensorPredictLdsBytes - TensorStopLdsBytes(num_class);
+  for (int k = 0; k < kTensorPredictSteps; ++k) {
+    if (TensorTileBytes(num_slots, kTensorPredictLadder[k], elem_size) <= budget) {
+      p.route = kTensorRouteTile;
+      p.rows = kTensorPredictLadder[k];
+      return p;
+    }
+  }
+  return p;
+}
+
 // One internal node.  theta: the threshold's bits (numerical), or the node's bitset as
 // word offset into the forest's cat_bits | words << 32 (categorical); slot_dt: slot << 8 | decision
 // type; children as in the tree, leaves as ~leaf

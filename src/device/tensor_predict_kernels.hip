@@ -26,6 +26,16 @@
 //                      contributions, for a window whose slots do not fit the smallest tile and for
 //                      trees whose children do not fit 16 bits.
 //   k_convert_scores   the finish of a row for the scores of that route.
+//   k_predict_tile_stop, k_predict_forest_stop
+//                      early-stopped scores (pred_early_stop) of the two routes.  The window is
+//                      walked in periods of stop_freq iterations.  A lane holds the id of a row of
+//                      its workgroup and reads the tile at [slot * pitch + id] (the compact matrix
+//                      at [slot * num_rows + row0 + id]): any lane can walk any row, so at a period
+//                      end the rows that go on are moved to the lowest lanes and emptied waves
+//                      stop walking (src/device/early_stop.h has the period end and its barriers).
+//                      A row's raw sums are stored where it stops and the workgroup finishes its
+//                      rows in place after its last tree, so neither route runs k_convert_scores.  The period end's LDS
+//                      comes out of the tile's budget (PlanTensorPredictStop).
 //
 // Sizes (gfx950: 160 KiB of LDS per CU).  A tile has 256 rows and at most kTensorPredictLdsBytes =
 // 52 KiB: 51 float32, 103 half or 25 float64 slots, and three workgroups (12 waves) on a CU.  The
@@ -42,6 +52,7 @@
 #include <type_traits>
 
 #include "device_common.h"
+#include "early_stop.h"
 #include "tensor_predict.h"
 
 namespace lgbm_amd {
@@ -112,6 +123,122 @@ __global__ __launch_bounds__(256) void k_predict_tile(TensorPredictArgs a) {
   for (int c = 0; c < a.num_class; ++c) a.out[row * a.num_class + c] = score[c];
 }
 
+// the trees of one period: stop_freq iterations, whole
+__device__ __forceinline__ int StopPeriodTrees(const TensorPredictArgs& a, int num_trees) {
+  return static_cast<int>(min(static_cast<long long>(a.stop_freq) * a.num_class, static_cast<long long>(num_trees)));
+}
+
+// A row of the stop kernels ends in two steps, so that no finish lies within the walk, where it
+// would hold a second copy of the sums in registers beside those of the rows that go on (141
+// registers and 3 waves per SIMD in place of k_predict_tile's 98 and 5): where the row stops, or
+// after the last tree, its raw sums go to `out` as they are ...
+__device__ __forceinline__ void StoreRawRow(const TensorPredictArgs& a, const double (&acc)[kMaxPredClasses],
+                                            long long row) {
+#pragma unroll
+  for (int c = 0; c < kMaxPredClasses; ++c) {
+    if (c < a.num_class) a.out[row * a.num_class + c] = acc[c];
+  }
+}
+
+// ... and when the workgroup has walked its last tree, thread i finishes row i of its nr rows in
+// place, whichever lane stored it (the barrier orders the workgroup's stores before these loads).
+// Every thread of the workgroup calls it
+__device__ __forceinline__ void FinishStoredRows(const TensorPredictArgs& a, long long row0, int nr) {
+  if (!(a.divisor > 0.0) && a.conv_kind <= 0) return;  // (raw scores; the same in every thread)
+  __syncthreads();
+  if (static_cast<int>(threadIdx.x) >= nr) return;
+  double* mine = a.out + (row0 + threadIdx.x) * a.num_class;
+  double score[kMaxPredClasses];
+  for (int c = 0; c < a.num_class; ++c) score[c] = mine[c];
+  FinishScoreRow(score, a.num_class, a.divisor, a.conv_kind, a.conv_param);
+  for (int c = 0; c < a.num_class; ++c) mine[c] = score[c];
+}
+
+template <typename T>
+__global__ __launch_bounds__(kStopRows) void k_predict_tile_stop(TensorPredictArgs a) {
+  extern __shared__ double s_tile[];  // the period end's arrays, then the tile
+  const StopLds lds = CarveStopLds(s_tile, a.num_class);
+  T* s_val = reinterpret_cast<T*>(s_tile + TensorStopLdsBytes(a.num_class) / 8);
+  const int tid = threadIdx.x;
+  const long long row0 = static_cast<long long>(blockIdx.x) * kStopRows;
+  const int nr = static_cast<int>(min(static_cast<long long>(kStopRows), static_cast<long long>(a.num_rows) - row0));
+  const int pitch = TensorTilePitch(kStopRows, static_cast<int>(sizeof(T)));
+  GatherTile(static_cast<const T*>(a.data), a.row_stride, a.col_stride, a.used, row0, nr, a.num_slots, pitch, s_val);
+  __syncthreads();
+  int rid = tid;
+  bool live = tid < nr;
+  double acc[kMaxPredClasses];
+#pragma unroll
+  for (int c = 0; c < kMaxPredClasses; ++c) acc[c] = 0.0;
+  const int per = StopPeriodTrees(a, a.num_trees);
+  // (t0, per and the rows left are the same in every thread: all of them reach every period end)
+  for (int t0 = 0, period = 0; t0 < a.num_trees; t0 += per, ++period) {
+    const int t1 = min(t0 + per, a.num_trees);
+    if (live) {
+      const T* mine = s_val + rid;
+      int k = 0;
+      for (int t = t0; t < t1; ++t) {
+        const int n0 = a.node_off[t];
+        const int leaf = PackedTreeLeaf(a.nodes + n0, a.node_off[t + 1] - n0, a.cat_bits, mine, pitch);
+        const double lv = a.leaf_value[a.leaf_off[t] + leaf];
+#pragma unroll
+        for (int c = 0; c < kMaxPredClasses; ++c) {
+          if (c == k) acc[c] += lv;
+        }
+        k = k + 1 == a.num_class ? 0 : k + 1;
+      }
+    }
+    if (t1 >= a.num_trees) break;
+    if (StopPeriodEnd(a, lds, period, acc, rid, live, [&](int r) { StoreRawRow(a, acc, row0 + r); }) == 0) break;
+  }
+  if (live) StoreRawRow(a, acc, row0 + rid);
+  FinishStoredRows(a, row0, nr);
+}
+
+template <typename T>
+__global__ __launch_bounds__(kStopRows) void k_predict_forest_stop(ForestArgs f, TensorPredictArgs a) {
+  __shared__ double s_stop[(2 * kStopRows * 8 + kStopRows * 4 + 2 * kStopWaves * 4) / 8];  // TensorStopLdsBytes at its most
+  const StopLds lds = CarveStopLds(s_stop, a.num_class);
+  const int tid = threadIdx.x;
+  const long long row0 = static_cast<long long>(blockIdx.x) * kStopRows;
+  const T* x = static_cast<const T*>(f.data) + row0;
+  int rid = tid;
+  bool live = row0 + tid < f.num_rows;
+  double acc[kMaxPredClasses];
+#pragma unroll
+  for (int c = 0; c < kMaxPredClasses; ++c) acc[c] = 0.0;
+  const int per = StopPeriodTrees(a, f.num_trees);
+  for (int t0 = 0, period = 0; t0 < f.num_trees; t0 += per, ++period) {
+    const int t1 = min(t0 + per, f.num_trees);
+    if (live) {
+      int k = 0;
+      for (int t = t0; t < t1; ++t) {
+        const int n0 = f.node_off[t], n1 = f.node_off[t + 1];
+        int leaf = 0;
+        if (n1 > n0) {
+          int node = 0;
+          while (node >= 0) {
+            const int gi = n0 + node;
+            const double v = static_cast<double>(x[static_cast<int64_t>(f.feature[gi]) * f.num_rows + rid]);
+            node = ForestGoesLeft(f, t, gi, v) ? f.left[gi] : f.right[gi];
+          }
+          leaf = ~node;
+        }
+        const double lv = f.leaf_value[f.leaf_off[t] + leaf];
+#pragma unroll
+        for (int c = 0; c < kMaxPredClasses; ++c) {
+          if (c == k) acc[c] += lv;
+        }
+        k = k + 1 == a.num_class ? 0 : k + 1;
+      }
+    }
+    if (t1 >= f.num_trees) break;
+    if (StopPeriodEnd(a, lds, period, acc, rid, live, [&](int r) { StoreRawRow(a, acc, row0 + r); }) == 0) break;
+  }
+  if (live) StoreRawRow(a, acc, row0 + rid);
+  FinishStoredRows(a, row0, static_cast<int>(min(static_cast<long long>(kStopRows), static_cast<long long>(f.num_rows) - row0)));
+}
+
 template <typename T>
 __global__ __launch_bounds__(kSlotsTileRows) void k_tensor_to_slots(TensorPredictArgs a, int nbatch, void* d_mat) {
   using O = std::conditional_t<std::is_same<T, double>::value, double, float>;
@@ -149,6 +276,11 @@ void PredictTensorTile(const TensorPredictArgs& a, hipStream_t s) {
   DispatchTensorElement(a.data_type, [&](auto* p) {
     using T = std::remove_cv_t<std::remove_pointer_t<decltype(p)>>;
     const size_t lds = static_cast<size_t>(TensorTileBytes(a.num_slots, a.tile_rows, static_cast<int>(sizeof(T))));
+    if (a.stop_freq > 0) {
+      // (PlanTensorPredictStop: one height, and the period end's bytes within the same budget)
+      hipLaunchKernelGGL(k_predict_tile_stop<T>, dim3(grid), dim3(kStopRows), lds + TensorStopLdsBytes(a.num_class), s, a);
+      return;
+    }
     if (a.leaf) hipLaunchKernelGGL((k_predict_tile<T, true>), dim3(grid), dim3(a.tile_rows), lds, s, a);
     else hipLaunchKernelGGL((k_predict_tile<T, false>), dim3(grid), dim3(a.tile_rows), lds, s, a);
   });
@@ -164,6 +296,13 @@ void TensorToSlots(const TensorPredictArgs& a, void* d_mat, hipStream_t s) {
     hipLaunchKernelGGL(k_tensor_to_slots<T>, dim3(static_cast<unsigned>(tiles * nbatch)), dim3(kSlotsTileRows), 0, s, a,
                        nbatch, d_mat);
   });
+}
+
+void PredictForestStop(const ForestArgs& f, const TensorPredictArgs& a, hipStream_t s) {
+  if (f.num_rows <= 0) return;
+  const dim3 grid(static_cast<unsigned>((f.num_rows + kStopRows - 1) / kStopRows));
+  if (f.is_double) hipLaunchKernelGGL(k_predict_forest_stop<double>, grid, dim3(kStopRows), 0, s, f, a);
+  else hipLaunchKernelGGL(k_predict_forest_stop<float>, grid, dim3(kStopRows), 0, s, f, a);
 }
 
 void ConvertTensorScores(const TensorPredictArgs& a, hipStream_t s) {

@@ -155,9 +155,11 @@ p("predict_raw_score", "bool", False, ["is_predict_raw_score", "predict_rawscore
 p("predict_leaf_index", "bool", False, ["is_predict_leaf_index", "leaf_index"], save=False, section=S)
 p("predict_contrib", "bool", False, ["is_predict_contrib", "contrib"], save=False, section=S)
 p("predict_disable_shape_check", "bool", False, save=False, section=S)
-p("pred_early_stop", "bool", False, save=False, section=S)
-p("pred_early_stop_freq", "int", 10, save=False, section=S)
-p("pred_early_stop_margin", "double", 10.0, save=False, section=S)
+p("pred_early_stop", "bool", False, save=False, section=S,
+  doc="stop the rows of a classification or ranking booster early (normal and raw scores); host matrices on the host predictor, GPU tensors on the device by the keyword of Booster.predict_device")
+p("pred_early_stop_freq", "int", 10, save=False, section=S, doc="iterations between two checks of a row's margin; must be > 0 when pred_early_stop applies")
+p("pred_early_stop_margin", "double", 10.0, save=False, section=S,
+  doc="a row stops when twice the absolute score (binary) or the largest minus the second largest class score is above it; must be >= 0")
 p("output_result", "string", "LightGBM_predict_result.txt",
   ["predict_result", "prediction_result", "predict_name", "prediction_name", "pred_name", "name_pred"],
   save=False, section=S)
