@@ -46,6 +46,8 @@ $(BUILD)/device/tensor_bin_kernels.hip.o: HIPEXTRA += -Xclang -target-feature -X
 $(BUILD)/device/bin_find_kernels.hip.o: HIPEXTRA += -Xclang -target-feature -Xclang -packed-fp32-ops
 # (the prediction of device matrices: its sums and transforms are compared bit for bit with the host's)
 $(BUILD)/device/tensor_predict_kernels.hip.o: HIPEXTRA += -Xclang -target-feature -Xclang -packed-fp32-ops
+# (the storage build moves integers only: the flag keeps the same rule)
+$(BUILD)/device/storage_kernels.hip.o: HIPEXTRA += -Xclang -target-feature -Xclang -packed-fp32-ops
 
 $(LIB): $(HOST_OBJS) $(DEV_OBJS)
 	@mkdir -p $(LIBDIR)
@@ -89,6 +91,11 @@ build_tsan/%.o: src/%.cpp $(HEADERS)
 build_tsan/tsan_driver: $(TSAN_OBJS) $(DEV_OBJS) tests/native/tsan_driver.cpp
 	$(CXX) $(filter-out -O3,$(CXXFLAGS)) $(TSAN_FLAGS) -o $@ tests/native/tsan_driver.cpp $(TSAN_OBJS) $(DEV_OBJS) \
 	  -fopenmp -L$(ROCM)/lib -lamdhip64 -lrccl -Wl,-rpath,$(ROCM)/lib
+
+# the storage window rule alone (a header: no device objects, no HIP runtime) with its table driver
+build_asan/storage_plan_driver: src/device/storage_plan.h tests/native/storage_plan_driver.cpp
+	@mkdir -p $(dir $@)
+	$(CXX) $(filter-out -O3 -fopenmp,$(CXXFLAGS)) $(ASAN_FLAGS) -o $@ tests/native/storage_plan_driver.cpp
 
 tsan: build_tsan/tsan_driver
 

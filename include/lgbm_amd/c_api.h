@@ -291,6 +291,30 @@ LIGHTGBM_C_EXPORT int LGBM_AMD_CscToSlots(BoosterHandle handle, const void* col_
 // boundaries): out[0] the stored entries of a segment, the share of a column that one wave takes,
 // out[1] the threads of a workgroup, out[2] the entries of a batch of the single-wave path
 LIGHTGBM_C_EXPORT int LGBM_AMD_CscLaunchInfo(int64_t* out);
+// the device learner's binned rows (test support; src/treelearner/gpu_learner_storage.cpp): a
+// copy of one buffer of the training set (data_idx 0) or of validation set data_idx - 1.  which
+// 0: the row image ([rows][row_words] 32-bit words), 1: the column image, 2: sp_ptr (int64),
+// 3: sp_bin (uint16), 4: the layout record, int64 values: row_words, groups, rows, 1 for
+// row-sparse training rows, then per group its byte in a row, its width code (0: 8 bits, 1: 16,
+// 2: 4), its nibble half (0 low, 1 high) and its byte in the column image.  *out_len is the
+// buffer's size in bytes (0: the learner holds no such buffer); it is copied when buffer_len
+// is at least that
+LIGHTGBM_C_EXPORT int LGBM_AMD_BoosterDeviceStorage(BoosterHandle handle, int data_idx, int which, int64_t buffer_len,
+                                                    int64_t* out_len, void* out);
+// the rule that plans the device build of the binned rows (src/device/storage_plan.h), evaluated
+// on the host (no GPU needed): rows of col_row_bytes column bytes and row_bytes row bytes each,
+// free_bytes of free device memory, keep 1 / 0 / -1 (the column image kept / not kept / by its
+// size).  out[0] whether the column image is kept, out[1] the rows of a window, out[2] the rows
+// between a window's columns, out[3] the window's bytes, out[4] the staging bytes, out[5] the
+// windows
+LIGHTGBM_C_EXPORT int LGBM_AMD_StoragePlan(int64_t rows, int64_t col_row_bytes, int64_t row_bytes, int64_t free_bytes,
+                                           int keep, int64_t* out);
+// how often a device learner's binned rows were built on the device / on the host in this process
+LIGHTGBM_C_EXPORT int LGBM_AMD_DeviceStorageStats(int64_t* device_builds, int64_t* host_builds);
+// the launch shape of the storage kernels (src/device/storage_kernels.hip): out[0] the rows of a
+// pack tile, out[1] the words of its slice, out[2] the threads of a workgroup, out[3] the rows
+// of a scan block
+LIGHTGBM_C_EXPORT int LGBM_AMD_StorageLaunchInfo(int64_t* out);
 // the rule that sizes the chunks of rows of a device prediction (src/boosting/predict_chunks.h),
 // evaluated on the host (no GPU needed): nrow rows within `budget` bytes, of which `fixed` are
 // held for the whole call, per_row for every row of a chunk and per_entry for every stored entry

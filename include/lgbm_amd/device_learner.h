@@ -163,6 +163,13 @@ class DeviceTreeLearner {
     (void)g; (void)h; (void)scales;
     return false;
   }
+  // a copy of one buffer of the binned rows of the training set (data_idx 0) or of validation
+  // set data_idx - 1: which 0 the row image, 1 the column image, 2 sp_ptr, 3 sp_bin, 4 the layout
+  // record (GPUTreeLearner::DebugStorage); a buffer the learner does not hold comes back empty
+  virtual bool DebugStorage(int data_idx, int which, std::vector<uint8_t>* out) {
+    (void)data_idx; (void)which; (void)out;
+    return false;
+  }
   // differential check of every leaf's device best split against the CPU split finder run
   // on the same (dequantised) histogram; a JSON report
   virtual std::string DebugCheckSplits(const Tree* tree) {
@@ -170,6 +177,9 @@ class DeviceTreeLearner {
     return "{}";
   }
 };
+
+// how many times a device learner's binned rows were built on the device / on the host so far
+void DeviceStorageStats(int64_t* device_builds, int64_t* host_builds);
 
 TreeLearner* CreateDeviceTreeLearner(const std::string& learner_type, const Config* config);
 

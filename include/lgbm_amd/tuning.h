@@ -33,6 +33,12 @@ constexpr int kRankPairCapMb = 6144;
 // NDCG / MAP on the device rank each document against every other of its query (one workgroup
 // per query): validation sets with a longer query are evaluated on the host
 constexpr int kQueryMetricDeviceMaxDocs = 16384;
+// the learner's binned rows are built on the device from this many cells (rows x groups) on, on
+// the host below.  Booster() on a constructed Dataset of 28 groups, median of 5, ms, host / device
+// (profiles/r23_device_storage.md): 300K rows 3.9 / 4.9, 1M 8.6 / 7.1 (ranges overlap), 3M 55.5 /
+// 15.6, 10M 233 / 66 -- the device build costs ~1.7 ms before its first byte, so the gate is the
+// smallest measured shape at which it is ahead by more than the spread, 3M x 28
+constexpr long long kDeviceStorageMinCells = 84000000;
 
 // ---- the variables: X(id, name, what it does)
 #define LGBM_AMD_KNOBS(X)                                                                                        \
@@ -72,6 +78,8 @@ constexpr int kQueryMetricDeviceMaxDocs = 16384;
   X(NibbleBins, "LGBM_AMD_NIBBLE_BINS", "1: 4-bit rows for groups of <= 16 bins (auto above 32 GiB)")          \
   X(ColumnCopy, "LGBM_AMD_COLUMN_COPY", "0/1: column-major copy of the bins (auto below 8 GiB)")                \
   X(SparseRows, "LGBM_AMD_SPARSE_ROWS", "0/1: row-sparse device storage (auto by density)")                    \
+  X(DeviceStorage, "LGBM_AMD_DEVICE_STORAGE", "0/1: the learner's binned rows (row words, column copy, row-sparse lists) built on the host / on the GPU from the group columns (auto by size; same bytes)")  \
+  X(StorageBudget, "LGBM_AMD_STORAGE_BUDGET", "n: bytes of free device memory that the device build of the binned rows plans its column window with (tests; auto: the free memory)")  \
   X(UniformBins, "LGBM_AMD_UNIFORM_BINS", "1: every group at the widest group's width")                        \
   X(GhInRows, "LGBM_AMD_GH_IN_ROWS", "0/1: (g, h) beside the bins in each row or apart")                       \
   X(RowAlignWords, "LGBM_AMD_ROW_ALIGN_WORDS", "n: row stride rounded up to n words")                          \

@@ -39,6 +39,10 @@ the kernels can be checked one by one against plain PyTorch references
   GPU tensor, the first step of the bin finder, by the kernels a training ``lgb.Dataset(gpu_tensor)``
   runs (src/device/bin_find_kernels.hip; reference BinMapper::FindBin's sort and run-length pass);
   :func:`bin_find_launch_info` gives their launch shape
+* :func:`device_storage` -- the binned rows a device booster trains on, as the learner holds them
+  in HBM: the row image, the column image, the row-sparse lists and the layout record that says
+  where each group sits (src/device/storage_kernels.hip builds them from the Dataset's group
+  columns); :func:`storage_launch_info` gives the kernels' launch shape
 
 There is no host fallback: the ops need a GPU and the in-tree library.
 """
@@ -51,7 +55,8 @@ from ..basic import _load_lib
 
 __all__ = ["gradients", "metric", "sample_rows", "forest_predict", "tensor_predict_launch_info", "leaf_sums", "add_leaf_values",
            "refit_launch_info", "csc_launch_info", "csr_group_bins", "csr_bin_launch_info",
-           "convert_scores", "cast_gradients", "custom_launch_info", "sample_distinct", "bin_find_launch_info"]
+           "convert_scores", "cast_gradients", "custom_launch_info", "sample_distinct", "bin_find_launch_info",
+           "device_storage", "storage_launch_info"]
 
 
 def _torch():
@@ -546,3 +551,42 @@ def cast_gradients(grad, hess):
                                               ctypes.c_int64(grad.numel()), _dev_ptr(out_g, torch.float32, "out"),
                                               _dev_ptr(out_h, torch.float32, "out")))
     return out_g, out_h
+
+
+_STORAGE_KINDS = {"rows": (0, np.uint32), "columns": (1, np.uint8), "sp_ptr": (2, np.int64), "sp_bin": (3, np.uint16),
+                  "layout": (4, np.int64)}
+
+
+def device_storage(booster, which, data_idx=0):
+    """One buffer of the binned rows of a ``device_type=gpu`` booster, copied back from the device.
+
+    ``which``: ``"rows"`` (uint32 ``[rows, row_words]``), ``"columns"`` (the column image, uint8),
+    ``"sp_ptr"`` (int64) / ``"sp_bin"`` (uint16) of row-sparse storage, or ``"layout"``: a dict of
+    ``row_words``, ``rows``, ``sparse_rows`` and per group ``byte`` (its byte in a row), ``width``
+    (bits: 4, 8 or 16), ``nibble`` (0 low / 1 high half of the byte) and ``column`` (its byte in the
+    column image).  ``data_idx`` 0 is the training set, 1 and above the validation sets in the order
+    they were added (a validation set has rows only).  A buffer the learner does not hold is empty."""
+    kind, dtype = _STORAGE_KINDS[which]
+    need = ctypes.c_int64(0)
+    _native_call("LGBM_AMD_BoosterDeviceStorage", booster.handle, ctypes.c_int(data_idx), ctypes.c_int(kind),
+                 ctypes.c_int64(0), ctypes.byref(need), None)
+    buf = np.zeros(need.value // np.dtype(dtype).itemsize, dtype=dtype)
+    _native_call("LGBM_AMD_BoosterDeviceStorage", booster.handle, ctypes.c_int(data_idx), ctypes.c_int(kind),
+                 ctypes.c_int64(buf.nbytes), ctypes.byref(need), buf.ctypes.data_as(ctypes.c_void_p))
+    if which == "rows":
+        return buf.reshape(-1, device_storage(booster, "layout", data_idx)["row_words"])
+    if which != "layout":
+        return buf
+    groups = buf[4:].reshape(-1, 4)
+    return {"row_words": int(buf[0]), "rows": int(buf[2]), "sparse_rows": bool(buf[3]),
+            "byte": groups[:, 0].copy(), "width": np.array([8, 16, 4])[groups[:, 1]], "nibble": groups[:, 2].copy(),
+            "column": groups[:, 3].copy()}
+
+
+def storage_launch_info():
+    """The launch shape of the storage kernels (src/device/storage_kernels.hip): ``tile_rows`` /
+    ``slice_words`` (the rows and 32-bit words of a tile of the row packing), ``block`` (threads of a
+    workgroup) and ``scan_rows`` (the rows of a block of the row-sparse pointer scan)."""
+    out = (ctypes.c_int64 * 4)()
+    _native_call("LGBM_AMD_StorageLaunchInfo", out)
+    return {"tile_rows": out[0], "slice_words": out[1], "block": out[2], "scan_rows": out[3]}

@@ -41,6 +41,8 @@
 #include "../device/kernels.h"
 #include "../device/refit_quant.h"
 #include "../device/score_convert.h"
+#include "../device/storage_build.h"
+#include "../device/storage_plan.h"
 #include "../device/tensor_predict.h"
 #include "../treelearner/growth_limits.h"
 #include "booster_device_buffers.h"
@@ -1862,6 +1864,46 @@ int LGBM_AMD_PredictChunkPlan(int64_t nrow, int64_t budget, int64_t fixed, int64
   out[0] = plan.chunk;
   out[1] = plan.entries;
   out[2] = plan.fits ? 1 : 0;
+  API_END();
+}
+
+int LGBM_AMD_BoosterDeviceStorage(BoosterHandle handle, int data_idx, int which, int64_t buffer_len, int64_t* out_len,
+                                  void* out) {
+  API_BEGIN();
+  std::vector<uint8_t> buf;
+  if (data_idx < 0 || which < 0 || which > 4 || !DeviceLearnerOf(handle)->DebugStorage(data_idx, which, &buf)) {
+    Log::Fatal("device storage: no dataset %d (0: training, from 1: validation sets) or no buffer %d", data_idx, which);
+  }
+  *out_len = static_cast<int64_t>(buf.size());
+  if (out != nullptr && buffer_len >= *out_len && !buf.empty()) std::memcpy(out, buf.data(), buf.size());
+  API_END();
+}
+
+int LGBM_AMD_StoragePlan(int64_t rows, int64_t col_row_bytes, int64_t row_bytes, int64_t free_bytes, int keep,
+                         int64_t* out) {
+  API_BEGIN();
+  if (rows < 1 || col_row_bytes < 0 || row_bytes < 0 || free_bytes < 0) {
+    Log::Fatal("StoragePlan: need rows >= 1 and no negative byte count");
+  }
+  const StoragePlan plan = PlanStorage(rows, col_row_bytes, row_bytes, free_bytes, keep);
+  out[0] = plan.keep_columns ? 1 : 0;
+  out[1] = plan.window_rows;
+  out[2] = plan.window_stride;
+  out[3] = plan.window_bytes;
+  out[4] = plan.staging_bytes;
+  out[5] = plan.windows;
+  API_END();
+}
+
+int LGBM_AMD_DeviceStorageStats(int64_t* device_builds, int64_t* host_builds) {
+  API_BEGIN();
+  DeviceStorageStats(device_builds, host_builds);
+  API_END();
+}
+
+int LGBM_AMD_StorageLaunchInfo(int64_t* out) {
+  API_BEGIN();
+  dev::StorageLaunchInfo(out);
   API_END();
 }
 

@@ -19,10 +19,25 @@ int GPUTreeLearner::AddValidData(const Dataset* valid, int ntpi, const double* s
   ValidSet vs;
   vs.num_data = valid->num_data();
   vs.ntpi = ntpi;
-  std::vector<uint8_t> host = RowMajorBins(valid, args_.words_per_row);
-  HIPCHECK(hipMalloc(&vs.bins, std::max<size_t>(1, host.size())));
-  valid_allocs_.push_back(vs.bins);
-  HIPCHECK(hipMemcpy(vs.bins, host.data(), host.size(), hipMemcpyHostToDevice));
+  // the rows in the training layout: packed on the device from a window of the set's group
+  // columns, or transposed here (UseDeviceStorage; the same bytes)
+  const bool device_storage = UseDeviceStorage(valid);
+  const double storage_t0 = common::NowSeconds();
+  if (device_storage) {
+    HIPCHECK(hipMalloc(&vs.bins, std::max<size_t>(1, static_cast<size_t>(vs.num_data) * 4 * static_cast<size_t>(args_.words_per_row))));
+    valid_allocs_.push_back(vs.bins);
+    BuildDeviceStorage(valid, args_.words_per_row, nullptr, static_cast<uint8_t*>(vs.bins));
+  } else {
+    std::vector<uint8_t> host = RowMajorBins(valid, args_.words_per_row);
+    HIPCHECK(hipMalloc(&vs.bins, std::max<size_t>(1, host.size())));
+    valid_allocs_.push_back(vs.bins);
+    HIPCHECK(hipMemcpy(vs.bins, host.data(), host.size(), hipMemcpyHostToDevice));
+  }
+  CountStorageBuild(device_storage);
+  if (common::PhaseTimer::Global().enabled()) {
+    common::PhaseTimer::Global().Add(device_storage ? "GPUTreeLearner::storage_build(device)" : "GPUTreeLearner::storage_build(host)",
+                                     (common::NowSeconds() - storage_t0) * 1e3);
+  }
   const size_t ns = static_cast<size_t>(vs.num_data) * ntpi;
   HIPCHECK(hipMalloc(reinterpret_cast<void**>(&vs.score), std::max<size_t>(1, ns) * sizeof(double)));
   valid_allocs_.push_back(vs.score);

@@ -198,12 +198,16 @@ void GPUTreeLearner::UploadData() {
   // training rows: the row-major word matrix, or row-sparse lists of stored bins (validation
   // sets always use the word layout)
   sparse_rows_ = UseSparseRows(wpr);
+  // the binned rows are built from the group columns on the device, or here on the host
+  // (UseDeviceStorage; the same bytes either way)
+  const bool device_storage = UseDeviceStorage(data_);
+  const double storage_t0 = common::NowSeconds();
   d_sp_ptr_ = nullptr;
   d_sp_bin_ = nullptr;
   d_bins_ = nullptr;
   d_gh_ = nullptr;
   if (sparse_rows_) {
-    UploadSparseRows();
+    if (!device_storage) UploadSparseRows();
   } else {
     // (g, h) interleaved at the end of each row, rows padded to 64 / 128 B (or 32-B multiples
     // when wider): a gathered row of the histogrammed child is then one cache line, where a
@@ -225,9 +229,13 @@ void GPUTreeLearner::UploadData() {
       const int al = std::max(1, std::atoi(e));
       if (!gh_rows) args_.row_words = (wpr + al - 1) / al * al;
     }
-    std::vector<uint8_t> host = RowMajorBins(data_, args_.row_words);
-    d_bins_ = Alloc<uint8_t>(host.size());
-    HIPCHECK(hipMemcpy(d_bins_, host.data(), host.size(), hipMemcpyHostToDevice));
+    if (device_storage) {
+      d_bins_ = Alloc<uint8_t>(static_cast<size_t>(num_data_) * 4 * static_cast<size_t>(args_.row_words));
+    } else {
+      std::vector<uint8_t> host = RowMajorBins(data_, args_.row_words);
+      d_bins_ = Alloc<uint8_t>(host.size());
+      HIPCHECK(hipMemcpy(d_bins_, host.data(), host.size(), hipMemcpyHostToDevice));
+    }
     if (gh_rows) d_gh_ = reinterpret_cast<dev::GH*>(static_cast<uint8_t*>(d_bins_) + 4 * static_cast<size_t>(row_words - 2));
   }
   // column-major copy for the partition kernels (one byte / short per row of the split column):
@@ -241,7 +249,12 @@ void GPUTreeLearner::UploadData() {
   bool col_copy = col_bytes <= (size_t(8) << 30);
   if (const char* cc = tuning::Get(tuning::Knob::ColumnCopy)) col_copy = cc[0] == '1';
   col_copy = col_copy || sparse_rows_;  // (the partition's only source of the split column)
-  if (col_copy) {
+  h_col_off_ = col_off;
+  if (device_storage) {
+    if (col_copy) d_bins_col_ = Alloc<uint8_t>(std::max<size_t>(1, col_bytes));
+    BuildDeviceStorage(data_, args_.row_words, d_bins_col_, static_cast<uint8_t*>(d_bins_));
+    if (sparse_rows_) BuildDeviceSparseRows();
+  } else if (col_copy) {
     std::vector<uint8_t> col(std::max<size_t>(1, col_bytes));
 #pragma omp parallel for schedule(static)
     for (int g = 0; g < num_groups_; ++g) {
@@ -264,6 +277,11 @@ void GPUTreeLearner::UploadData() {
     }
     d_bins_col_ = Alloc<uint8_t>(col.size());
     HIPCHECK(hipMemcpy(d_bins_col_, col.data(), col.size(), hipMemcpyHostToDevice));
+  }
+  CountStorageBuild(device_storage);
+  if (common::PhaseTimer::Global().enabled()) {
+    common::PhaseTimer::Global().Add(device_storage ? "GPUTreeLearner::storage_build(device)" : "GPUTreeLearner::storage_build(host)",
+                                     (common::NowSeconds() - storage_t0) * 1e3);
   }
   // features
   std::vector<dev::Feature> feats(num_features_);
@@ -1847,12 +1865,7 @@ void GPUTreeLearner::UploadSparseRows() {
   HIPCHECK(hipMemcpy(d_sp_ptr_, ptr.data(), sizeof(int64_t) * ptr.size(), hipMemcpyHostToDevice));
   d_sp_bin_ = Alloc<uint16_t>(ent.size());
   HIPCHECK(hipMemcpy(d_sp_bin_, ent.data(), sizeof(uint16_t) * ent.size(), hipMemcpyHostToDevice));
-  // threads per row: a row of mean length fits the kSparsePer entries each thread loads up front
-  const double mean = static_cast<double>(ptr[n]) / std::max<data_size_t>(1, n);
-  sp_team_ = 4;
-  while (sp_team_ < 64 && sp_team_ * dev::kSparsePerThread < mean) sp_team_ *= 2;
-  Log::Info("device learner: row-sparse storage, %.2f stored bins per row (%d groups), %d threads per row", mean,
-            num_groups_, sp_team_);
+  SetSparseTeam(static_cast<double>(ptr[n]) / std::max<data_size_t>(1, n));
 }
 
 // row-major copy of a dataset's storage columns in this learner's layout (each group at its

@@ -94,6 +94,7 @@ class GPUTreeLearner : public SerialTreeLearner, public DeviceTreeLearner {
                       std::vector<int8_t>* bin_valid, double* sums) override;
   bool DebugGradients(std::vector<float>* g, std::vector<float>* h, double* scales) override;
   std::string DebugCheckSplits(const Tree* tree) override;  // gpu_self_check.cpp
+  bool DebugStorage(int data_idx, int which, std::vector<uint8_t>* out) override;
   bool RenewTreeOutputOnDevice(Tree* tree, const ObjectiveFunction* obj, int tree_id) override;
   TreeStats LastTreeStats() const override { return last_stats_; }
   // refit from the leaf matrix (gpu_learner_refit.cpp); one process only
@@ -163,6 +164,12 @@ class GPUTreeLearner : public SerialTreeLearner, public DeviceTreeLearner {
   bool ForcedGathered() const { return distributed_ && !data_parallel_ && !voting_ && world_ > 1; }
   void UploadSparseRows();
   std::vector<uint8_t> RowMajorBins(const Dataset* d, int row_words) const;
+  // the same buffers built on the device from the group columns (gpu_learner_storage.cpp)
+  bool UseDeviceStorage(const Dataset* d) const;
+  void BuildDeviceStorage(const Dataset* d, int row_words, uint8_t* col_image, uint8_t* row_image);
+  void BuildDeviceSparseRows();
+  void SetSparseTeam(double mean_stored);
+  static void CountStorageBuild(bool on_device);
   template <typename T>
   T* Alloc(size_t n);
 
@@ -369,6 +376,7 @@ class GPUTreeLearner : public SerialTreeLearner, public DeviceTreeLearner {
   double* d_scales_ = nullptr;
   uint32_t* d_absmax_ = nullptr;
   uint8_t* d_bins_col_ = nullptr;
+  std::vector<int64_t> h_col_off_;  // [num_groups + 1] byte of each group's column in the column image
   // row layout (KArgs::bin_bytes / word_g0): per group its byte in a row and width, the
   // word holding it; per word its first group (+ sentinel) and width
   std::vector<int32_t> h_gbyte_, h_word_of_group_, h_word_g0_;
