@@ -139,8 +139,10 @@ class GBDT {
                             int start_iteration, int num_iteration, DevicePredictKind kind, double* out);
   // the same kernels on a row-major matrix in device memory, into out_len doubles of device
   // memory (raw scores, leaf indices or contributions); what is not applicable is an error
+  // (shap_kernel: the contribution kernel, dev::ShapChoice of src/device/shap_plan.h -- 0: by its rule)
   void PredictDeviceBuffers(const void* d_data, bool is_double, int64_t nrow, int ncol, int start_iteration,
-                            int num_iteration, DevicePredictKind kind, double* d_out, int64_t out_len);
+                            int num_iteration, DevicePredictKind kind, double* d_out, int64_t out_len,
+                            int shap_kernel = 0);
   // every kind of prediction, Normal included, of a strided matrix in the memory of HIP device
   // device_id (element (r, c) at d_data[r * row_stride + c * col_stride] of the C API's data_type
   // float32 / float64 / float16 / bfloat16) into out_len doubles of that device's memory, as
@@ -171,7 +173,7 @@ class GBDT {
   // applicable is an error
   void PredictCSRDeviceBuffers(const void* d_indptr, bool indptr_is_64, const int32_t* d_indices, const void* d_data,
                                bool is_double, int64_t nrow, int64_t nelem, int start_iteration, int num_iteration,
-                               DevicePredictKind kind, double* d_out, int64_t out_len);
+                               DevicePredictKind kind, double* d_out, int64_t out_len, int shap_kernel = 0);
   // the compact matrix of host CSR rows evaluated on the host (tests; needs no device): the
   // sorted features the window's trees split on into `used` (room for every feature, or null) and
   // their count into *num_used; with `matrix` (row-major [rows][*num_used], of the data's type)
@@ -194,7 +196,7 @@ class GBDT {
   void PredictCSCDeviceBuffers(const void* d_col_ptr, bool col_ptr_is_64, const int32_t* d_indices,
                                const void* d_data, bool is_double, int64_t ncol, int64_t nelem, int64_t nrow,
                                int start_iteration, int num_iteration, DevicePredictKind kind, double* d_out,
-                               int64_t out_len);
+                               int64_t out_len, int shap_kernel = 0);
   // the compact matrix of the rows [row0, row0 + rows) of a host CSC matrix evaluated on the host
   // (tests; needs no device), as CsrToSlotsOnHost gives it for CSR rows
   void CscToSlotsOnHost(const void* col_ptr, bool col_ptr_is_64, const int32_t* indices, const void* data,
@@ -329,7 +331,7 @@ class GBDT {
   // the checks of kind, class count and out_len
   template <typename Forest>
   void UploadForDeviceBuffers(Forest* forest, DevicePredictKind kind, bool slots, int64_t nrow, int64_t out_len,
-                              int start_iteration, int num_iteration);
+                              int start_iteration, int num_iteration, int shap_kernel);
   // ... and PredictDeviceTensor / TensorPredictOnHost, after InitPredict: the checks of the matrix,
   // the column and class counts, and into `a` (dev::TensorPredictArgs) the strides, the kind and
   // what the host predictor does to a row of raw scores, early stopping included where it applies

@@ -477,6 +477,20 @@ LIGHTGBM_C_EXPORT int LGBM_AMD_TensorPredictStopPlan(int32_t num_slots, int32_t 
 // steps of the ladder of tile heights, out[1..n] the heights, tallest first, out[n + 1] the LDS
 // bytes a tile may take, out[n + 2] the most leaves of a tree whose nodes are packed
 LIGHTGBM_C_EXPORT int LGBM_AMD_TensorPredictLaunchInfo(int64_t* out);
+// ---- which kernel computes SHAP contributions on the device (src/device/shap_plan.h), a pure
+// function (no GPU): a call of `rows` rows on a forest of num_class trees per iteration whose
+// largest tree has max_leaves leaves, whose tree with the most path elements has max_tree_elems
+// and whose longest path has max_path_len elements, bias element included (0: a node of data_count
+// 0, no tables), of num_features features; shap_kernel 0 the rule, 1 rows-on-lanes, 2
+// leaves-on-lanes.  out[0] the kernel (0 rows-on-lanes, 1 leaves-on-lanes, -1 none: the host
+// predicts, a device-buffer call is an error), out[1] the waves W of a leaves-on-lanes workgroup
+// (1 for rows-on-lanes), out[2] whether the accumulator is in LDS, out[3] the workgroup's LDS bytes
+LIGHTGBM_C_EXPORT int LGBM_AMD_ShapPlan(int64_t rows, int32_t num_class, int32_t max_leaves, int32_t max_tree_elems,
+                                        int32_t max_path_len, int32_t num_features, int shap_kernel, int64_t* out);
+// its launch shape (out has room for 8 values): out[0] the lanes of a wave, out[1] = n the steps of
+// the ladder of W, out[2..n + 1] the ladder, widest first, out[n + 2] the LDS bytes a workgroup may
+// take, out[n + 3] the row count below which the rule picks leaves-on-lanes
+LIGHTGBM_C_EXPORT int LGBM_AMD_ShapLaunchInfo(int64_t* out);
 // ---- custom objectives and metrics on device tensors (a booster trained with device_type=gpu)
 // the HIP device of the booster's device learner, or -1 (a CPU booster, a loaded model)
 LIGHTGBM_C_EXPORT int LGBM_AMD_BoosterDeviceId(BoosterHandle handle, int* out);

@@ -39,6 +39,14 @@ constexpr int kQueryMetricDeviceMaxDocs = 16384;
 // 15.6, 10M 233 / 66 -- the device build costs ~1.7 ms before its first byte, so the gate is the
 // smallest measured shape at which it is ahead by more than the spread, 3M x 28
 constexpr long long kDeviceStorageMinCells = 84000000;
+// SHAP contributions: a call of fewer rows than this takes the leaves-on-lanes kernel (a workgroup
+// per row), one of as many or more the rows-on-lanes kernel (a lane per row; src/device/shap_plan.h).
+// Median of 7, ms, leaves / rows (profiles/r24_shap_small_batches.md): 28 features, 100 trees x 63
+// leaves: 16,384 rows 34.3 / 61.9, 32,768 64.1 / 63.4, 65,536 125 / 62.5; 2,000 features: 16,384
+// 41.5 / 81.9, 32,768 79.2 / 91.1, 65,536 154 / 98.7.  Rows-on-lanes is first ahead at 32,768 rows
+// on the narrow model and at 65,536 on the wide one; 32,768 it is, since at 65,536 the narrow model
+// would pay twice the time of rows-on-lanes where the wide one pays 13 % at 32,768
+constexpr long long kShapLeafMaxRows = 32768;
 
 // ---- the variables: X(id, name, what it does)
 #define LGBM_AMD_KNOBS(X)                                                                                        \

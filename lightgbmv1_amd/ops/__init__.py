@@ -203,9 +203,10 @@ def sample_rows(n, fraction=1.0, seed=3, goss=False, top_rate=0.2, other_rate=0.
 
 
 _FOREST_KINDS = {"raw": 1, "leaf": 2, "contrib": 3}  # C_API_PREDICT_RAW_SCORE / LEAF_INDEX / CONTRIB
+_SHAP_KERNELS = {"auto": 0, "rows": 1, "leaves": 2}  # dev::ShapChoice (src/device/shap_plan.h)
 
 
-def forest_predict(booster, X, kind="raw", start_iteration=0, num_iteration=-1):
+def forest_predict(booster, X, kind="raw", start_iteration=0, num_iteration=-1, shap_kernel="auto"):
     """Predictions of ``booster`` for the rows of ``X``, a contiguous float32 or float64 GPU
     tensor ``[n, ncol]``, computed and left on the GPU as a float64 tensor: raw scores
     ``[n, classes]`` (``kind="raw"``), leaf indices ``[n, trees]`` (``"leaf"``) or SHAP
@@ -220,10 +221,18 @@ def forest_predict(booster, X, kind="raw", start_iteration=0, num_iteration=-1):
     A ``torch.sparse_csc`` GPU tensor is taken the same way (int32 or int64 ``ccol_indices``;
     int64 ``row_indices`` are converted to int32 on the device): only the columns the trees split
     on are read (src/device/csc_kernels.hip), and of several stored entries on one cell the last
-    stored one is the value."""
+    stored one is the value.
+
+    ``shap_kernel`` picks the kernel of ``kind="contrib"``: ``"rows"`` (a lane per row: large
+    calls), ``"leaves"`` (a workgroup per row, a lane per leaf: small batches;
+    src/device/shap_leaf_kernels.hip) or ``"auto"``, by the row count (:func:`shap_launch_info`).
+    ``"leaves"`` raises where that kernel cannot serve the model."""
     torch = _torch()
     if kind not in _FOREST_KINDS:
         raise LightGBMError("kind must be one of 'raw', 'leaf', 'contrib', got %r" % (kind,))
+    if shap_kernel not in _SHAP_KERNELS:
+        raise LightGBMError("shap_kernel must be one of 'auto', 'rows', 'leaves', got %r" % (shap_kernel,))
+    which = ctypes.c_int(_SHAP_KERNELS[shap_kernel])
     if not isinstance(X, torch.Tensor) or X.dim() != 2 or X.dtype not in (torch.float32, torch.float64):
         raise LightGBMError("X must be a 2-d float32 or float64 torch tensor on the GPU")
     sparse = X.layout in (torch.sparse_csr, torch.sparse_csc)
@@ -254,20 +263,32 @@ def forest_predict(booster, X, kind="raw", start_iteration=0, num_iteration=-1):
             ctypes.c_int(0 if X.dtype == torch.float32 else 1), ctypes.c_int64(crow.numel() - 1),
             ctypes.c_int64(values.numel()), ctypes.c_int64(n), ctypes.c_int(_FOREST_KINDS[kind]),
             ctypes.c_int(start), ctypes.c_int(num), _dev_ptr(out, torch.float64, "out"),
-            ctypes.c_int64(out.numel())))
+            ctypes.c_int64(out.numel()), which))
         return out
     if sparse:
         _check(_lib().LGBMAMD_OpForestPredictCSR(
             booster.handle, ptrs[0], ctypes.c_int(2 if crow.dtype == torch.int32 else 3), ptrs[1], ptrs[2],
             ctypes.c_int(0 if X.dtype == torch.float32 else 1), ctypes.c_int64(n), ctypes.c_int64(values.numel()),
             ctypes.c_int(_FOREST_KINDS[kind]), ctypes.c_int(start), ctypes.c_int(num),
-            _dev_ptr(out, torch.float64, "out"), ctypes.c_int64(out.numel())))
+            _dev_ptr(out, torch.float64, "out"), ctypes.c_int64(out.numel()), which))
         return out
     _check(_lib().LGBMAMD_OpForestPredict(booster.handle, data, ctypes.c_int(0 if X.dtype == torch.float32 else 1),
                                        ctypes.c_int64(n), ctypes.c_int32(ncol), ctypes.c_int(_FOREST_KINDS[kind]),
                                        ctypes.c_int(start), ctypes.c_int(num), _dev_ptr(out, torch.float64, "out"),
-                                       ctypes.c_int64(out.numel())))
+                                       ctypes.c_int64(out.numel()), which))
     return out
+
+
+def shap_launch_info():
+    """The launch shape of the contribution kernels (src/device/shap_plan.h): ``lanes`` (a wave:
+    the rows of a rows-on-lanes tile, the leaves a leaves-on-lanes wave takes at a time),
+    ``wave_ladder`` (the waves W of a leaves-on-lanes workgroup, widest first: the plan picks the
+    first that fits, ``LGBM_AMD_ShapPlan``), ``lds_bytes`` (what a workgroup may take) and
+    ``leaf_max_rows`` (a call of fewer rows takes leaves-on-lanes)."""
+    out = (ctypes.c_int64 * 8)()
+    _native_call("LGBM_AMD_ShapLaunchInfo", out)
+    n = out[1]
+    return {"lanes": out[0], "wave_ladder": list(out[2:2 + n]), "lds_bytes": out[2 + n], "leaf_max_rows": out[3 + n]}
 
 
 def tensor_predict_launch_info():

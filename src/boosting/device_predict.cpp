@@ -30,6 +30,7 @@
 #include "../device/csc_slots.h"
 #include "../device/csr_slots.h"
 #include "../device/kernels.h"
+#include "../device/shap_plan.h"
 #include "predict_chunks.h"
 #include "shap_paths.h"
 #include "lgbm_amd/boosting.h"
@@ -75,13 +76,21 @@ struct DeviceBuffers {
 // the forest (and, for contributions, its path tables) of one prediction call on the device
 class DeviceForest {
  public:
-  // false: the contribution kernel cannot run this forest (the host predicts)
+  // false: no contribution kernel can run this forest (the host predicts)
   // slots: the forest walks a compact matrix of the features it splits on (CSR rows, CSC columns)
+  // rows, shap_kernel: the rows of the whole call and the caller's dev::ShapChoice, from which
+  // src/device/shap_plan.h picks the contribution kernel (one kernel for every chunk of a call)
   bool Upload(const std::vector<const Tree*>& trees, int num_class, int num_features, DevicePredictKind kind,
-              hipStream_t s, bool slots = false) {
+              hipStream_t s, bool slots = false, int64_t rows = 0, int shap_kernel = dev::kShapChoiceAuto) {
     kind_ = kind;
     flat_.Build(trees);
-    if (kind == DevicePredictKind::Contrib && (!paths_.Build(trees) || !paths_.FitsDevice())) return false;
+    if (kind == DevicePredictKind::Contrib) {
+      const bool tables = paths_.Build(trees);
+      const dev::ShapModel model{num_class, flat_.MaxLeaves(), paths_.max_tree_elems,
+                                 tables ? paths_.max_path_len : 0, num_features};
+      plan_ = dev::PlanShap(rows, model, shap_kernel);
+      if (plan_.kernel == dev::kShapKernelNone) return false;
+    }
     f_.num_class = num_class;
     f_.num_trees = static_cast<int32_t>(trees.size());
     f_.node_off = b_.Upload(flat_.node_off, s);
@@ -115,7 +124,14 @@ class DeviceForest {
       a_.pairs = b_.Upload(paths_.pairs, s);
       a_.expected = b_.Upload(paths_.expected, s);
       a_.ratio = b_.Upload(paths_.ratio, s);
-      phi_in_lds_ = dev::ShapLdsBytes(a_, true) <= static_cast<size_t>(dev::kShapLdsBytes);
+      if (plan_.kernel == dev::kShapKernelLeaves) {
+        a_.max_tree_elems = paths_.max_tree_elems;
+        a_.leaf_waves = plan_.waves;
+        a_.tree_group_off = b_.Upload(paths_.tree_group_off, s);
+        a_.group_feature = b_.Upload(paths_.group_feature, s);
+        a_.group_off = b_.Upload(paths_.group_off, s);
+        a_.fold_elem = b_.Upload(paths_.fold_elem, s);
+      }
     }
     return true;
   }
@@ -152,7 +168,10 @@ class DeviceForest {
   }
   // device bytes a launch over `rows` rows allocates besides its input and output
   size_t ScratchBytes(int64_t rows) const {
-    if (kind_ != DevicePredictKind::Contrib || phi_in_lds_) return 0;
+    if (kind_ != DevicePredictKind::Contrib || plan_.phi_in_lds) return 0;
+    if (plan_.kernel == dev::kShapKernelLeaves) {
+      return static_cast<size_t>(dev::ShapLeafGrid(rows)) * (a_.num_features + 1) * sizeof(double);
+    }
     const int tiles = static_cast<int>((rows + dev::kShapLanes - 1) / dev::kShapLanes);
     return static_cast<size_t>(dev::ShapTileGrid(tiles)) * (a_.num_features + 1) * dev::kShapLanes * sizeof(double);
   }
@@ -172,15 +191,20 @@ class DeviceForest {
       dev::ShapArgs a = a_;
       a.num_tiles = static_cast<int32_t>((rows + dev::kShapLanes - 1) / dev::kShapLanes);
       a.out = d_out;
-      if (!phi_in_lds_) {
+      if (!plan_.phi_in_lds) {
         const size_t need = ScratchBytes(rows);
         if (need > phi_bytes_) {
           phi_tiles_ = b_.Alloc(need);
           phi_bytes_ = need;
         }
-        a.phi_tiles = static_cast<double*>(phi_tiles_);
       }
-      dev::ShapForest(f, a, s);
+      if (plan_.kernel == dev::kShapKernelLeaves) {
+        a.phi_rows = plan_.phi_in_lds ? nullptr : static_cast<double*>(phi_tiles_);
+        dev::ShapForestLeaves(f, a, s);
+      } else {
+        a.phi_tiles = plan_.phi_in_lds ? nullptr : static_cast<double*>(phi_tiles_);
+        dev::ShapForest(f, a, s);
+      }
     } else {
       dev::PredictForest(f, s);
     }
@@ -211,7 +235,7 @@ class DeviceForest {
   DeviceBuffers b_;
   dev::ForestArgs f_{};
   dev::ShapArgs a_{};
-  bool phi_in_lds_ = true;
+  dev::ShapPlan plan_{dev::kShapKernelRows, 1, 1, 0};
   void* phi_tiles_ = nullptr;
   size_t phi_bytes_ = 0;
 };
@@ -435,7 +459,7 @@ bool GBDT::PredictChunksOnDevice(Source* src, int64_t nrow, int start_iteration,
   bool ran = false;
   {
     DeviceForest forest;
-    if (forest.Upload(trees, ntpi, max_feature_idx_ + 1, kind, s, Source::kSlots)) {
+    if (forest.Upload(trees, ntpi, max_feature_idx_ + 1, kind, s, Source::kSlots, nrow)) {
       const int64_t per_out = forest.OutPerRow();
       const SourceBytes in = src->Measure(forest);
       // rows per chunk (predict_chunks.h): input, output and the accumulator tiles within most of
@@ -484,13 +508,20 @@ bool GBDT::PredictChunksOnDevice(Source* src, int64_t nrow, int start_iteration,
 
 template <typename Forest>
 void GBDT::UploadForDeviceBuffers(Forest* forest, DevicePredictKind kind, bool slots, int64_t nrow, int64_t out_len,
-                                  int start_iteration, int num_iteration) {
+                                  int start_iteration, int num_iteration, int shap_kernel) {
   if (kind == DevicePredictKind::Normal) Log::Fatal("device buffers are predicted as raw scores, leaf indices or contributions");
   if (num_tree_per_iteration_ > dev::kMaxPredClasses) {
     Log::Fatal("forest prediction on the device handles at most %d trees per iteration", dev::kMaxPredClasses);
   }
   const std::vector<const Tree*> trees = PredictWindowTrees(start_iteration, num_iteration);
-  if (!forest->Upload(trees, num_tree_per_iteration_, max_feature_idx_ + 1, kind, nullptr, slots)) {
+  if (shap_kernel < dev::kShapChoiceAuto || shap_kernel > dev::kShapChoiceLeaves) {
+    Log::Fatal("shap_kernel %d is not 0 (auto), 1 (rows) or 2 (leaves)", shap_kernel);
+  }
+  if (!forest->Upload(trees, num_tree_per_iteration_, max_feature_idx_ + 1, kind, nullptr, slots, nrow, shap_kernel)) {
+    if (shap_kernel == dev::kShapChoiceLeaves) {
+      Log::Fatal("the leaves-on-lanes contribution kernel cannot serve this model: not even one wave's paths and "
+                 "terms fit its %d bytes of LDS, or the rows-on-lanes kernel's limits apply", dev::kShapLdsBytes);
+    }
     Log::Fatal("contributions on the device need paths of at most %d distinct features and data counts on every node",
                dev::kShapMaxPathLen - 1);
   }
@@ -510,13 +541,14 @@ bool GBDT::PredictDenseOnDevice(const void* data, bool is_double, int64_t nrow, 
 }
 
 void GBDT::PredictDeviceBuffers(const void* d_data, bool is_double, int64_t nrow, int ncol, int start_iteration,
-                                int num_iteration, DevicePredictKind kind, double* d_out, int64_t out_len) {
+                                int num_iteration, DevicePredictKind kind, double* d_out, int64_t out_len,
+                                int shap_kernel) {
   if (ncol != max_feature_idx_ + 1) {
     Log::Fatal("The number of features in data (%d) is not the same as it was in training data (%d).", ncol,
                max_feature_idx_ + 1);
   }
   DeviceForest forest;
-  UploadForDeviceBuffers(&forest, kind, false, nrow, out_len, start_iteration, num_iteration);
+  UploadForDeviceBuffers(&forest, kind, false, nrow, out_len, start_iteration, num_iteration, shap_kernel);
   if (nrow > 0) forest.Run(d_data, is_double, true, nrow, ncol, d_out, nullptr);
   HIPCHECK(hipStreamSynchronize(nullptr));
   ++g_device_predictions;
@@ -626,7 +658,7 @@ void GBDT::PredictDeviceTensor(const void* d_data, int data_type, int64_t nrow, 
   a.out = d_out;
   const DeviceGuard guard(device_id);
   DeviceForest forest;
-  if (!forest.Upload(trees, num_tree_per_iteration_, max_feature_idx_ + 1, kind, nullptr, true)) {
+  if (!forest.Upload(trees, num_tree_per_iteration_, max_feature_idx_ + 1, kind, nullptr, true, nrow)) {
     Log::Fatal("contributions on the device need paths of at most %d distinct features and data counts on every node",
                dev::kShapMaxPathLen - 1);
   }
@@ -780,10 +812,10 @@ bool GBDT::PredictCSROnDevice(const void* indptr, bool indptr_is_64, const int32
 void GBDT::PredictCSRDeviceBuffers(const void* d_indptr, bool indptr_is_64, const int32_t* d_indices,
                                    const void* d_data, bool is_double, int64_t nrow, int64_t nelem,
                                    int start_iteration, int num_iteration, DevicePredictKind kind, double* d_out,
-                                   int64_t out_len) {
+                                   int64_t out_len, int shap_kernel) {
   if (nrow < 0 || nelem < 0) Log::Fatal("CSR device buffers: %lld rows, %lld entries", static_cast<long long>(nrow), static_cast<long long>(nelem));
   DeviceForest forest;
-  UploadForDeviceBuffers(&forest, kind, true, nrow, out_len, start_iteration, num_iteration);
+  UploadForDeviceBuffers(&forest, kind, true, nrow, out_len, start_iteration, num_iteration, shap_kernel);
   if (nrow > 0) {
     DeviceBuffers b;
     void* d_mat = b.Alloc(static_cast<size_t>(nrow) * forest.NumSlots() * (is_double ? 8 : 4));
@@ -812,13 +844,13 @@ bool GBDT::PredictCSCOnDevice(const void* col_ptr, bool col_ptr_is_64, const int
 void GBDT::PredictCSCDeviceBuffers(const void* d_col_ptr, bool col_ptr_is_64, const int32_t* d_indices,
                                    const void* d_data, bool is_double, int64_t ncol, int64_t nelem, int64_t nrow,
                                    int start_iteration, int num_iteration, DevicePredictKind kind, double* d_out,
-                                   int64_t out_len) {
+                                   int64_t out_len, int shap_kernel) {
   if (nrow < 0 || nelem < 0 || ncol < 0) {
     Log::Fatal("CSC device buffers: %lld rows, %lld columns, %lld entries", static_cast<long long>(nrow),
                static_cast<long long>(ncol), static_cast<long long>(nelem));
   }
   DeviceForest forest;
-  UploadForDeviceBuffers(&forest, kind, true, nrow, out_len, start_iteration, num_iteration);
+  UploadForDeviceBuffers(&forest, kind, true, nrow, out_len, start_iteration, num_iteration, shap_kernel);
   if (nrow > 0) {
     const int nslot = forest.NumSlots();
     // (the full pointer stays on the device: a slot names its feature's column, if the matrix has it)

@@ -160,12 +160,40 @@ bool ShapPathTables::Build(const std::vector<const Tree*>& trees) {
     }
     tree_leaf_off.push_back(static_cast<int32_t>(leaf_value.size()));
   }
+  BuildFoldLists();
   // (D - j) / (D + 1) for every path of D elements, at ShapRatioOffset(D) + j
   ratio.assign(dev::ShapRatioOffset(max_path_len) + 1, 0.0);
   for (int d = 1; d < max_path_len; ++d) {
     for (int j = 0; j < d; ++j) ratio[dev::ShapRatioOffset(d) + j] = (d - j) / static_cast<double>(d + 1);
   }
   return true;
+}
+
+void ShapPathTables::BuildFoldLists() {
+  const int nt = static_cast<int>(tree_leaf_off.size()) - 1;
+  tree_group_off.assign(1, 0);
+  group_off.assign(1, 0);
+  group_feature.clear();
+  fold_elem.clear();
+  max_tree_elems = 0;
+  std::vector<int32_t> order;
+  for (int t = 0; t < nt; ++t) {
+    const int e0 = leaf_elem_off[tree_leaf_off[t]], e1 = leaf_elem_off[tree_leaf_off[t + 1]];
+    max_tree_elems = std::max(max_tree_elems, e1 - e0);
+    order.resize(e1 - e0);
+    for (int e = e0; e < e1; ++e) order[e - e0] = e - e0;
+    std::stable_sort(order.begin(), order.end(),
+                     [&](int32_t x, int32_t y) { return elem_feature[e0 + x] < elem_feature[e0 + y]; });
+    for (size_t i = 0; i < order.size(); ++i) {
+      if (i == 0 || elem_feature[e0 + order[i]] != elem_feature[e0 + order[i - 1]]) {
+        if (i > 0) group_off.push_back(static_cast<int32_t>(fold_elem.size()));
+        group_feature.push_back(elem_feature[e0 + order[i]]);
+      }
+      fold_elem.push_back(order[i]);
+    }
+    if (!order.empty()) group_off.push_back(static_cast<int32_t>(fold_elem.size()));
+    tree_group_off.push_back(static_cast<int32_t>(group_feature.size()));
+  }
 }
 
 void ShapPathTables::HostArgs(dev::ShapArgs* a) const {
@@ -180,14 +208,11 @@ void ShapPathTables::HostArgs(dev::ShapArgs* a) const {
   a->pairs = pairs.data();
   a->expected = expected.data();
   a->ratio = ratio.data();
-}
-
-bool ShapPathTables::FitsDevice() const {
-  if (max_path_len > dev::kShapMaxPathLen) return false;
-  dev::ShapArgs a{};
-  a.max_path_len = max_path_len;
-  a.mask_words = mask_words;
-  return dev::ShapLdsBytes(a, false) <= static_cast<size_t>(dev::kShapLdsBytes);
+  a->max_tree_elems = max_tree_elems;
+  a->tree_group_off = tree_group_off.data();
+  a->group_feature = group_feature.data();
+  a->group_off = group_off.data();
+  a->fold_elem = fold_elem.data();
 }
 
 void EvalPathTables(const dev::ForestArgs& f, const dev::ShapArgs& a, double* out) {

@@ -57,13 +57,19 @@ struct ShapPathTables {
   std::vector<double> leaf_value, elem_zero, expected, ratio;
   int max_path_len = 1;  // longest path in elements, bias element included
   int mask_words = 0;    // 32-bit words of the widest tree's decision mask
+  // The fold lists of the leaves-on-lanes kernel (src/device/shap_leaf_kernels.hip): a tree's
+  // elements grouped by feature, features ascending, a group's elements in table order (leaf, then
+  // element: a stable sort) -- the order in which the rows-on-lanes kernel adds a feature's terms.
+  // fold_elem names an element by its position among its tree's elements
+  std::vector<int32_t> tree_group_off, group_feature, group_off, fold_elem;
+  int max_tree_elems = 0;  // elements of the tree that has the most
 
   // false: a node on some path has data_count 0 (its zero fraction would divide by zero)
   bool Build(const std::vector<const Tree*>& trees);
+  // the fold lists from the element tables (the last step of Build)
+  void BuildFoldLists();
   // the table fields of `a` pointing at these host vectors
   void HostArgs(dev::ShapArgs* a) const;
-  // the device kernel can run these tables (path length and LDS limits)
-  bool FitsDevice() const;
 };
 
 // The contributions of f.num_rows rows (f.data: host memory) from the tables, with the kernel's

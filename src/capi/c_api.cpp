@@ -41,6 +41,7 @@
 #include "../device/kernels.h"
 #include "../device/refit_quant.h"
 #include "../device/score_convert.h"
+#include "../device/shap_plan.h"
 #include "../device/storage_build.h"
 #include "../device/storage_plan.h"
 #include "../device/tensor_predict.h"
@@ -546,7 +547,8 @@ class Booster {
   bool DevicePredictGate(int data_type, int64_t nrow, int64_t ncol, int predict_type, const Config& cfg,
                          DevicePredictKind* kind) const {
     if (!DeviceKindOf(predict_type, kind)) return false;
-    if (cfg.pred_early_stop || nrow < (*kind == DevicePredictKind::Contrib ? kDeviceContribMinRows : 1024)) return false;
+    if (cfg.pred_early_stop) return false;
+    if (*kind == DevicePredictKind::Contrib ? !DeviceContribRows(nrow) : nrow < 1024) return false;
     if (data_type != C_API_DTYPE_FLOAT32 && data_type != C_API_DTYPE_FLOAT64) return false;
     if (cfg.device_type != "gpu" && config_.device_type != "gpu") return false;
     const char* e = tuning::Get(tuning::Knob::HostPredict);
@@ -634,8 +636,19 @@ class Booster {
     *out_len = static_cast<int64_t>(nrow) * boosting_->NumPredictOneRow(start_iteration, num_iteration, false, true);
   }
 
-  // rows from which contributions of a host matrix go to the device (profiles/r07_device_shap.md)
-  static constexpr int kDeviceContribMinRows = 1024;
+  // The rows at which contributions of a host matrix go to the device.  From 1,024 rows on, as
+  // scores and leaf indices do (profiles/r07_device_shap.md).  Below, the leaves-on-lanes kernel
+  // serves small batches in about 4 ms whatever their rows: the device path, transfers included,
+  // is ahead of the host from kDeviceContribMinRows rows (profiles/r24_shap_small_batches.md: 64
+  // rows, host 5.7 ms / device 4.2 ms on 28 features and 4.4 / 4.7 on 2,000; 256 rows 21.9 / 4.2
+  // and 17.3 / 6.9).  The range ends at kDeviceContribSmallRows: the device stays ahead up to
+  // 1,023 rows too, but calls just below the gate of 1,024 keep the host they have always had
+  static constexpr int kDeviceContribMinRows = 64;
+  static constexpr int kDeviceContribSmallRows = 512;
+  static bool DeviceContribRows(int64_t nrow) {
+    if (nrow >= 1024) return true;
+    return nrow >= kDeviceContribMinRows && nrow <= kDeviceContribSmallRows && nrow < tuning::kShapLeafMaxRows;
+  }
   static bool DeviceKindOf(int predict_type, DevicePredictKind* kind) {
     switch (predict_type) {
       case C_API_PREDICT_NORMAL: *kind = DevicePredictKind::Normal; return true;
@@ -2158,6 +2171,32 @@ int LGBM_AMD_TensorPredictLaunchInfo(int64_t* out) {
   API_END();
 }
 
+int LGBM_AMD_ShapPlan(int64_t rows, int32_t num_class, int32_t max_leaves, int32_t max_tree_elems,
+                      int32_t max_path_len, int32_t num_features, int shap_kernel, int64_t* out) {
+  API_BEGIN();
+  if (rows < 0 || num_class < 1 || max_leaves < 1 || max_tree_elems < 0 || max_path_len < 0 || num_features < 0 ||
+      shap_kernel < dev::kShapChoiceAuto || shap_kernel > dev::kShapChoiceLeaves) {
+    Log::Fatal("ShapPlan: need rows >= 0, num_class >= 1, max_leaves >= 1, sizes >= 0 and shap_kernel 0, 1 or 2");
+  }
+  const dev::ShapPlan plan = dev::PlanShap(
+      rows, dev::ShapModel{num_class, max_leaves, max_tree_elems, max_path_len, num_features}, shap_kernel);
+  out[0] = plan.kernel;
+  out[1] = plan.waves;
+  out[2] = plan.phi_in_lds;
+  out[3] = static_cast<int64_t>(plan.lds_bytes);
+  API_END();
+}
+
+int LGBM_AMD_ShapLaunchInfo(int64_t* out) {
+  API_BEGIN();
+  out[0] = dev::kShapLanes;
+  out[1] = dev::kShapLeafWaveSteps;
+  for (int k = 0; k < dev::kShapLeafWaveSteps; ++k) out[2 + k] = dev::kShapLeafWaveLadder[k];
+  out[2 + dev::kShapLeafWaveSteps] = dev::kShapLdsBytes;
+  out[3 + dev::kShapLeafWaveSteps] = tuning::kShapLeafMaxRows;
+  API_END();
+}
+
 int LGBM_AMD_BoosterDeviceId(BoosterHandle handle, int* out) {
   API_BEGIN();
   const auto booster_lock = ReadLock(handle);
@@ -2199,35 +2238,36 @@ namespace lgbm_amd {
 // memory (booster_device_buffers.h; lightgbmv1_amd.ops.forest_predict): no row gate, no host round trip
 void BoosterPredictDeviceBuffers(BoosterHandle handle, const void* d_data, int data_type, int64_t nrow, int32_t ncol,
                                  int predict_type, int start_iteration, int num_iteration, double* d_out,
-                                 int64_t out_len) {
+                                 int64_t out_len, int shap_kernel) {
   const DevicePredictKind kind = Booster::DeviceBufferKind(predict_type, data_type);
   const auto booster_lock = WriteLock(handle);
   static_cast<Booster*>(handle)->boosting()->PredictDeviceBuffers(
-      d_data, data_type == C_API_DTYPE_FLOAT64, nrow, ncol, start_iteration, num_iteration, kind, d_out, out_len);
+      d_data, data_type == C_API_DTYPE_FLOAT64, nrow, ncol, start_iteration, num_iteration, kind, d_out, out_len,
+      shap_kernel);
 }
 // ... of CSR arrays in device memory (a sparse_csr tensor)
 void BoosterPredictCSRDeviceBuffers(BoosterHandle handle, const void* d_indptr, int indptr_type,
                                     const int32_t* d_indices, const void* d_data, int data_type, int64_t nrow,
                                     int64_t nelem, int predict_type, int start_iteration, int num_iteration,
-                                    double* d_out, int64_t out_len) {
+                                    double* d_out, int64_t out_len, int shap_kernel) {
   const DevicePredictKind kind = Booster::DeviceBufferKind(predict_type, data_type);
   Booster::CheckDevicePointerType(indptr_type, "indptr");
   const auto booster_lock = WriteLock(handle);
   static_cast<Booster*>(handle)->boosting()->PredictCSRDeviceBuffers(
       d_indptr, indptr_type == C_API_DTYPE_INT64, d_indices, d_data, data_type == C_API_DTYPE_FLOAT64, nrow, nelem,
-      start_iteration, num_iteration, kind, d_out, out_len);
+      start_iteration, num_iteration, kind, d_out, out_len, shap_kernel);
 }
 // ... and of CSC arrays in device memory (a sparse_csc tensor)
 void BoosterPredictCSCDeviceBuffers(BoosterHandle handle, const void* d_col_ptr, int col_ptr_type,
                                     const int32_t* d_indices, const void* d_data, int data_type, int64_t ncol,
                                     int64_t nelem, int64_t nrow, int predict_type, int start_iteration,
-                                    int num_iteration, double* d_out, int64_t out_len) {
+                                    int num_iteration, double* d_out, int64_t out_len, int shap_kernel) {
   const DevicePredictKind kind = Booster::DeviceBufferKind(predict_type, data_type);
   Booster::CheckDevicePointerType(col_ptr_type, "col_ptr");
   const auto booster_lock = WriteLock(handle);
   static_cast<Booster*>(handle)->boosting()->PredictCSCDeviceBuffers(
       d_col_ptr, col_ptr_type == C_API_DTYPE_INT64, d_indices, d_data, data_type == C_API_DTYPE_FLOAT64, ncol, nelem, nrow,
-      start_iteration, num_iteration, kind, d_out, out_len);
+      start_iteration, num_iteration, kind, d_out, out_len, shap_kernel);
 }
 }  // namespace lgbm_amd
 

@@ -155,13 +155,15 @@ LIGHTGBM_C_EXPORT const char* LGBMAMD_OpLastError() { return g_op_error.c_str();
 // a booster's forest on a row-major float32 / float64 matrix in device memory: raw scores
 // [nrow][classes], leaf indices [nrow][trees] or SHAP contributions [nrow][classes * (F + 1)]
 // (predict_type: C_API_PREDICT_RAW_SCORE / LEAF_INDEX / CONTRIB) into out_len doubles of device
-// memory, with the kernels of LGBM_BoosterPredictForMat's device path
+// memory, with the kernels of LGBM_BoosterPredictForMat's device path.  shap_kernel picks the
+// contribution kernel: 0 by the rule of src/device/shap_plan.h, 1 rows-on-lanes, 2 leaves-on-lanes
+// (an error where that kernel cannot serve the model)
 LIGHTGBM_C_EXPORT int LGBMAMD_OpForestPredict(BoosterHandle handle, const void* d_data, int data_type, int64_t nrow,
                                               int32_t ncol, int predict_type, int start_iteration, int num_iteration,
-                                              double* d_out, int64_t out_len) {
+                                              double* d_out, int64_t out_len, int shap_kernel) {
   return Guard([&] {
     BoosterPredictDeviceBuffers(handle, d_data, data_type, nrow, ncol, predict_type, start_iteration, num_iteration,
-                                d_out, out_len);
+                                d_out, out_len, shap_kernel);
   });
 }
 
@@ -172,10 +174,10 @@ LIGHTGBM_C_EXPORT int LGBMAMD_OpForestPredict(BoosterHandle handle, const void* 
 LIGHTGBM_C_EXPORT int LGBMAMD_OpForestPredictCSR(BoosterHandle handle, const void* d_indptr, int indptr_type,
                                                  const int32_t* d_indices, const void* d_data, int data_type,
                                                  int64_t nrow, int64_t nelem, int predict_type, int start_iteration,
-                                                 int num_iteration, double* d_out, int64_t out_len) {
+                                                 int num_iteration, double* d_out, int64_t out_len, int shap_kernel) {
   return Guard([&] {
     BoosterPredictCSRDeviceBuffers(handle, d_indptr, indptr_type, d_indices, d_data, data_type, nrow, nelem,
-                                   predict_type, start_iteration, num_iteration, d_out, out_len);
+                                   predict_type, start_iteration, num_iteration, d_out, out_len, shap_kernel);
   });
 }
 
@@ -187,10 +189,10 @@ LIGHTGBM_C_EXPORT int LGBMAMD_OpForestPredictCSC(BoosterHandle handle, const voi
                                                  const int32_t* d_indices, const void* d_data, int data_type,
                                                  int64_t ncol, int64_t nelem, int64_t nrow, int predict_type,
                                                  int start_iteration, int num_iteration, double* d_out,
-                                                 int64_t out_len) {
+                                                 int64_t out_len, int shap_kernel) {
   return Guard([&] {
     BoosterPredictCSCDeviceBuffers(handle, d_col_ptr, col_ptr_type, d_indices, d_data, data_type, ncol, nelem, nrow,
-                                   predict_type, start_iteration, num_iteration, d_out, out_len);
+                                   predict_type, start_iteration, num_iteration, d_out, out_len, shap_kernel);
   });
 }
 

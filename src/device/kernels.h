@@ -609,6 +609,16 @@ struct ShapArgs {
   const double* ratio{};           // (D - j) / (D + 1) at ShapRatioOffset(D) + j, D < kShapMaxPathLen
   double* phi_tiles{};             // null: the tile's accumulator is in LDS; else [grid][F + 1][kShapLanes]
   double* out{};                   // [num_rows][num_class][F + 1]
+  // leaves-on-lanes only (src/device/shap_leaf_kernels.hip; src/device/shap_plan.h picks the kernel):
+  // the fold lists of src/boosting/shap_paths.h -- a tree's elements grouped by feature, each group
+  // in table order -- and the shape of the workgroup
+  int32_t max_tree_elems{};         // elements of the tree that has the most
+  int32_t leaf_waves{};             // W: waves of a workgroup, one tree of the batch each
+  const int32_t* tree_group_off{};  // [num_trees + 1] groups of each tree
+  const int32_t* group_feature{};   // [groups] real feature index
+  const int32_t* group_off{};       // [groups + 1] the group's entries of fold_elem
+  const int32_t* fold_elem{};       // [elements] an element's position among its tree's elements
+  double* phi_rows{};               // null: the row's accumulator is in LDS; else [grid][F + 1]
 };
 constexpr int ShapRatioOffset(int d) { return d * (d - 1) / 2; }
 // LDS bytes of a workgroup with / without the accumulator tile ((F + 1) rows of kShapLanes + 1)
@@ -616,6 +626,8 @@ size_t ShapLdsBytes(const ShapArgs& a, bool phi_in_lds);
 // workgroups of the launch when the accumulator is a global tile (a.phi_tiles holds that many)
 int ShapTileGrid(int num_tiles);
 void ShapForest(const ForestArgs& f, const ShapArgs& a, hipStream_t s);
+// the same contributions by leaves-on-lanes: one workgroup of a.leaf_waves waves per row
+void ShapForestLeaves(const ForestArgs& f, const ShapArgs& a, hipStream_t s);
 
 // a chunk of CSR rows into the compact column-major matrix ([num_slots][num_rows]) that the
 // forest kernels read with a slot-rewritten ForestArgs::feature and row_major = 0

@@ -7,7 +7,9 @@
 // src/io/tree.cpp) in its per-leaf form, from the path tables of src/boosting/shap_paths.cpp: a
 // leaf's contribution to phi[feature of element i] is UnwoundPathSum(path, D, i) * (one_i -
 // zero_i) * leaf_value after the leaf's D merged path elements were ExtendPath'ed in table
-// order.  One lane owns one row and a workgroup of kShapLanes rows walks every tree, leaf and
+// order (ShapLeafTerms, src/device/shap_leaf.h, shared with the leaves-on-lanes kernel of small
+// batches, src/device/shap_leaf_kernels.hip).  One lane owns one row and a workgroup of
+// kShapLanes rows walks every tree, leaf and
 // element together: the tables are wave-uniform loads and nothing diverges; a lane differs from
 // its neighbours only in the 0 / 1 one-fractions, which are selects.  Per lane:
 //   * the decisions of all internal nodes of the current tree, as a bit mask in LDS
@@ -21,21 +23,13 @@
 // does not depend on scheduling.  src/boosting/shap_paths.cpp has the same arithmetic on the
 // host (EvalPathTables), which the tests hold against the recursive host predictor.
 #include "device_common.h"
-#include "forest_decision.h"
+#include "shap_leaf.h"
+#include "shap_plan.h"
 
 namespace lgbm_amd {
 namespace dev {
 
 namespace {
-
-constexpr int kPhiLdsStride = kShapLanes + 1;  // (+1: the transposed read-out is free of bank conflicts)
-
-template <typename T, bool ROW_MAJOR>
-__device__ __forceinline__ double ForestValue(const ForestArgs& f, int64_t row, int feat) {
-  const T* x = static_cast<const T*>(f.data);
-  return ROW_MAJOR ? static_cast<double>(x[row * f.num_cols + feat])
-                   : static_cast<double>(x[static_cast<int64_t>(feat) * f.num_rows + row]);
-}
 
 template <typename T, bool ROW_MAJOR>
 __global__ __launch_bounds__(256) void k_predict_leaf(ForestArgs f) {
@@ -91,50 +85,9 @@ __global__ __launch_bounds__(kShapLanes) void k_shap_forest(ForestArgs f, ShapAr
           mask[w * kShapLanes] = m;
         }
         for (int l = l0; l < l1; ++l) {
-          const int e0 = a.leaf_elem_off[l], D = a.leaf_elem_off[l + 1] - e0;
-          // ExtendPath of the bias element, then of elements 1..D; ones: bit d = one-fraction of element d
-          unsigned long long ones_lo = 0, ones_hi = 0;
-          pw[0] = 1.0;
-          for (int d = 1; d <= D; ++d) {
-            const int e = e0 + d - 1;
-            bool one = true;
-            for (int p = a.elem_pair_off[e], p1 = a.elem_pair_off[e + 1]; p < p1; ++p) {
-              const int pr = a.pairs[p], node = pr >> 1;
-              const uint32_t went_left = (mask[(node >> 5) * kShapLanes] >> (node & 31)) & 1u;
-              one = one && went_left == static_cast<uint32_t>(pr & 1);
-            }
-            if (d < 64) ones_lo |= static_cast<unsigned long long>(one) << d;
-            else ones_hi |= static_cast<unsigned long long>(one) << (d - 64);
-            const double zero = a.elem_zero[e];
-            const double dp1 = static_cast<double>(d + 1);
-            double carry = 0.0;  // pweight[i + 1] after its own scaling by the zero fraction
-            for (int i = d - 1; i >= 0; --i) {
-              const double p = pw[i * kShapLanes];
-              const double up = p * (i + 1) / dp1;
-              pw[(i + 1) * kShapLanes] = carry + (one ? up : 0.0);
-              carry = zero * p * (d - i) / dp1;
-            }
-            pw[0] = carry;
-          }
-          // UnwoundPathSum of every element, both of its branches computed and selected
-          const double lv = a.leaf_value[l];
-          const double* ratio = a.ratio + ShapRatioOffset(D);
-          const double Dp1 = static_cast<double>(D + 1);
-          const double top = pw[D * kShapLanes];
-          for (int i = 1; i <= D; ++i) {
-            const int e = e0 + i - 1;
-            const double zero = a.elem_zero[e];
-            const bool one = ((i < 64 ? ones_lo >> i : ones_hi >> (i - 64)) & 1ull) != 0;
-            double next_one = top, total = 0.0;
-            for (int j = D - 1; j >= 0; --j) {
-              const double p = pw[j * kShapLanes];
-              const double r = ratio[j];
-              const double q = (one ? next_one * Dp1 : p) / (one ? static_cast<double>(j + 1) : zero);
-              total += one ? q : q / r;
-              next_one = p - q * zero * r;
-            }
-            phi[a.elem_feature[e] * fs] += total * ((one ? 1.0 : 0.0) - zero) * lv;
-          }
+          ShapLeafTerms<kShapLanes, kShapLanes>(a, l, pw, mask, [&](int e, double term) {
+            phi[a.elem_feature[e] * fs] += term;
+          });
         }
       }
       __syncthreads();
@@ -172,9 +125,7 @@ void PredictForestLeaf(const ForestArgs& f, hipStream_t s) {
 }
 
 size_t ShapLdsBytes(const ShapArgs& a, bool phi_in_lds) {
-  size_t doubles = static_cast<size_t>(a.max_path_len) * kShapLanes;
-  if (phi_in_lds) doubles += static_cast<size_t>(a.num_features + 1) * kPhiLdsStride;
-  return doubles * sizeof(double) + static_cast<size_t>(a.mask_words) * kShapLanes * sizeof(uint32_t);
+  return ShapRowsLdsBytes(a.max_path_len, a.mask_words, a.num_features, phi_in_lds);
 }
 
 int ShapTileGrid(int num_tiles) { return std::max(1, std::min(num_tiles, 2048)); }

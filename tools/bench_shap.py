@@ -9,6 +9,15 @@ model (28 features, 100 trees x 63 leaves by default), in rows per second:
   python tools/bench_shap.py                       # 10K, 100K and 1M rows
   python tools/bench_shap.py --rows 10000 --trees 20
 
+  python tools/bench_shap.py --small                 # the two kernels and the host on small batches
+  python tools/bench_shap.py --small --features 2000 --train-rows 20000   # ... on a wide model
+
+--small times, per row count, the two contribution kernels through ops.forest_predict
+(shap_kernel="rows" / "leaves"), the device with its transfers (a numpy matrix to the GPU, the
+leaves-on-lanes kernel below the kernel threshold and rows-on-lanes from it on, the result back),
+Booster.predict as it is routed, and the host predictor: after a warm-up of each, --repeats
+rounds that take the paths in turn inside this process; median, minimum and maximum in ms.
+
 Every path is warmed up once per row count, then timed --repeats times (median); a path whose
 first timed run takes longer than --slow-s is timed once (its warm-up alone if that took four
 times as long), and the host is not run above
@@ -58,6 +67,54 @@ def max_abs_leaf(node):
     return max(max_abs_leaf(node["left_child"]), max_abs_leaf(node["right_child"]))
 
 
+def small_batches(bst, rows_of, rows, repeats, host_max_rows):
+    """{rows: {path: [median, min, max] ms}} of the paths of --small, taken in turn"""
+    import torch
+
+    from lightgbmv1_amd import ops
+
+    threshold = ops.shap_launch_info()["leaf_max_rows"]
+    table = {}
+    for n in rows:
+        X = rows_of(n)
+        Xd = torch.tensor(X, device="cuda")
+
+        def kernel(which):
+            ops.forest_predict(bst, Xd, kind="contrib", shap_kernel=which)
+            torch.cuda.synchronize()
+
+        def transfers():
+            which = "leaves" if n < threshold else "rows"
+            return ops.forest_predict(bst, torch.tensor(X, device="cuda"), kind="contrib", shap_kernel=which).cpu()
+
+        def host():
+            os.environ["LGBM_AMD_HOST_PREDICT"] = "1"
+            try:
+                bst.predict(X, pred_contrib=True)
+            finally:
+                del os.environ["LGBM_AMD_HOST_PREDICT"]
+
+        paths = {"rows_kernel": lambda: kernel("rows"), "leaves_kernel": lambda: kernel("leaves"),
+                 "device_with_transfers": transfers,
+                 "booster_predict": lambda: bst.predict(X, pred_contrib=True, device_type="gpu")}
+        if n <= host_max_rows:
+            paths["host"] = host
+        before = device_predictions()
+        for fn in paths.values():
+            fn()  # warm-up
+        routed = device_predictions() - before - 3  # (the three ops calls count too)
+        times = {k: [] for k in paths}
+        for _ in range(repeats):
+            for k, fn in paths.items():
+                t = time.perf_counter()
+                fn()
+                times[k].append(1e3 * (time.perf_counter() - t))
+        table[str(n)] = {k: [round(statistics.median(v), 3), round(min(v), 3), round(max(v), 3)] for k, v in times.items()}
+        table[str(n)]["booster_predict_on"] = "device" if routed > 0 else "host"
+        print("# %d rows: %s" % (n, json.dumps(table[str(n)])), file=sys.stderr, flush=True)
+    return table
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--rows", type=int, nargs="*", default=[10_000, 100_000, 1_000_000])
@@ -68,6 +125,8 @@ def main():
     ap.add_argument("--slow-s", type=float, default=8.0)
     ap.add_argument("--host-max-rows", type=int, default=100_000)
     ap.add_argument("--host-threads", type=int, default=16)
+    ap.add_argument("--small", action="store_true", help="the small-batch table instead of the throughput")
+    ap.add_argument("--features", type=int, default=28, help="28: the Higgs shape; else normal columns")
     args = ap.parse_args()
 
     import torch
@@ -78,16 +137,28 @@ def main():
 
     if lgb.device_count() < 1:
         raise SystemExit("bench_shap.py needs a HIP device")
-    Xt, yt, _ = make_higgs(args.train_rows)
+    if args.features == 28:
+        Xt, yt, _ = make_higgs(args.train_rows)
+        rows_of = lambda n: make_higgs(n, start=args.train_rows)[0]
+    else:
+        rng = np.random.RandomState(7)
+        Xt = rng.randn(args.train_rows, args.features).astype(np.float32)
+        yt = (Xt[:, ::7].sum(axis=1) + rng.randn(args.train_rows) > 0).astype(np.float32)
+        rows_of = lambda n: np.random.RandomState(n).randn(n, args.features).astype(np.float32)
     params = {"objective": "binary", "device_type": "gpu", "num_leaves": args.leaves, "max_bin": 63,
               "min_data_in_leaf": 20, "verbose": -1, "num_threads": args.host_threads}
     bst = lgb.train(params, lgb.Dataset(Xt, yt, params=params), num_boost_round=args.trees)
     scale = 2.0 ** -52 * sum(max_abs_leaf(t["tree_structure"]) for t in bst.dump_model()["tree_info"])
     result = {"tool": "bench_shap", "features": int(Xt.shape[1]), "trees": bst.num_trees(), "leaves": args.leaves,
               "host_threads": args.host_threads, "rows": {}}
+    if args.small:
+        rows = args.rows if args.rows != ap.get_default("rows") else [1, 16, 64, 256, 1024, 4096, 16384]
+        result["small"] = small_batches(bst, rows_of, rows, args.repeats, args.host_max_rows)
+        print(json.dumps(result))
+        return
     worst = 0.0
     for n in args.rows:
-        X = make_higgs(n, start=args.train_rows)[0]
+        X = rows_of(n)
         Xd = torch.tensor(X, device="cuda")
         row = {}
 
@@ -103,7 +174,7 @@ def main():
         if device_predictions() != before:
             row["capi"] = {"rows_per_s": n / t, "seconds": t, "runs": k}
         elif n < 1024:
-            row["capi"] = "host (below the row gate of 1024)"
+            row["capi"] = "host (the row gate)"
         else:
             raise SystemExit("the C API prediction did not run on the device")
         t, k, dev = timed(run_ops, args.repeats, args.slow_s)
